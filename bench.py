@@ -1,14 +1,21 @@
 """Headline benchmark: training images/sec of the TaskPrompter ViT-L hot path, 512x512, 6 tasks (BASELINE.json),
 on N MI355X of one node (one process per GPU; RCCL all-reduce of gradients over xGMI via DistributedDataParallel).
 
-    python bench.py --gpus 1 --steps K --warmup W [--config ns6|cfg2|cfg3|cfg4|cfg5] [--prec x3f|bf16|x3] [--batch B]
+    python bench.py --gpus 1 --steps K --warmup W [--config ns6|cfg2|cfg3|cfg4|cfg5] [--prec x3f|bf16|x3] [--batch B] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = forward + MultiTaskLoss + backward (+ gradient all-reduce) + clip_grad_norm_ + Adam step on one synthetic batch
 that is already resident in HBM (TaskPrompter/utils/train_utils.py:32-51), including the re-packing of every weight the optimizer
-changed.  Weak scaling: the per-GPU batch is fixed.  Prints ONE JSON line on rank 0 (contract in the task statement).
+changed.  Weak scaling: the per-GPU batch is fixed.  Prints ONE JSON line on rank 0: `value` (images/s) and `ms_per_step` come from the
+K timed steps alone.  Inputs and weights are seeded, so the same arguments give the same inputs on every run; `--dump-outputs DIR`
+writes what the last timed step computed (bench.write_dump) for comparing two builds output for output.
 
-The HEADLINE (`value`, `ms_per_step`, `fwd_ms_per_img`, `roofline`, `parity`) is the tolerance-compliant arithmetic mode `x3f`
+A plain run stops there.  Everything below is measured only with `--full` (the `--no-*` flags drop single legs of it):
+  host         — the host time to enqueue one step against its wall time
+  fwd_ms_per_img — the forward-only latency (eval mode, no autograd)
+
+The HEADLINE (`value`, `ms_per_step`; with --full `fwd_ms_per_img`, `roofline`, `parity`) is the tolerance-compliant arithmetic mode `x3f`
 (--prec x3f, the default): the reference computes in fp32 (taskprompter.py:195-214), north_star asks for 1e-3 per task head, bf16 misses
 it (1.5e-2) and x3f meets it (2.6e-5) — forward = 3 bf16 MFMAs per product on hi / lo split operands, backward bf16 on the hi planes.
   roofline     — the headline mode's dominant kernel (gemm_ring3_kernel: the 256-row LDS-DMA MFMA GEMM on split planes): bf16 MFMA work of
@@ -96,6 +103,14 @@ def parse():
                          "only works under tests/bench_emulated.py, which routes ops.call to the test emulator")
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: host enqueue share, forward-only latency, roofline, parity, fast_mode, "
+                         "full_fp32_mode, ref_batch, torch_rocm_baseline and cpu_baseline (the --no-* flags still drop single legs); without it "
+                         "a run sets up, warms up, times --steps steps and prints the line with those records null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline's last timed step computed as DIR/<name>.npy (float32 / float64): "
+                         "a seeded sample of every task output of its forward (out_<task>), its loss, and a seeded sample of every parameter "
+                         "after its optimizer step (params); at most 48 MB in all")
     ap.add_argument("--config", default="ns6", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=0,
                     help="per-GPU batch (weak scaling); 0 = the config's default.  ns6: 126*1030 token rows = 507 row tiles of 256, so the "
@@ -124,7 +139,7 @@ def parse():
     ap.add_argument("--gemm-variant", type=int, default=None,
                     help="A/B: mtt_gemm_desc.variant for every GEMM left at AUTO (1 = general kernel, 3 = LDS-DMA kernel, 11 = general epilogue everywhere)")
     ap.add_argument("--cpu-roofline", action="store_true",
-                    help="(host-logic tests, --device cpu only) keep the instrumented roofline step — wall-clock stamps instead of HIP events — so "
+                    help="(host-logic tests, --device cpu --full only) keep the instrumented roofline step — wall-clock stamps instead of HIP events — so "
                          "that a gloo run exercises what every rank does around it under DDP")
     ap.add_argument("--no-head-prologue", action="store_true",
                     help="A/B: ConvHead's BatchNorm + GELU as a pass of their own writing the fp32 activated map (round 5) instead of riding on the "
@@ -512,6 +527,47 @@ def graphed_ref_batch(cfg_name, prec, limit_s=240):
         return dict(error=repr(e)[:200])
 
 
+DUMP_OUT_ELEMS = 8 << 20       # --dump-outputs: task-output elements in all (32 MB of float32), shared evenly by the outputs
+DUMP_PARAM_ELEMS = 4 << 20     # parameter elements in all (16 MB), at most 4096 per parameter
+
+
+def _sample(t, k, name):
+    """a fixed sample of k elements of t (all of them if it has no more), as a float32 vector on t's device: the indices come from a
+    generator on that device seeded by the name, so two runs or two builds sample the same elements, and drawing them inside the timed
+    step costs two small launches and no host work"""
+    import zlib
+    t = t.detach()
+    if t.numel() <= k:
+        return t.float().flatten().clone()
+    g = torch.Generator(device=t.device).manual_seed(zlib.crc32(name.encode()))
+    idx = torch.randint(t.numel(), (k,), generator=g, device=t.device)
+    return torch.take(t, idx).float()
+
+
+def _sample_outputs(out):
+    """seeded samples of the forward's task outputs (nested dicts: InvPT's inter_preds) as {out_<task>[_<sub>]: device vector}"""
+    flat = {}
+    for t, v in out.items():
+        for sub, vv in ([(None, v)] if torch.is_tensor(v) else (v.items() if isinstance(v, dict) else [])):
+            if torch.is_tensor(vv):
+                flat["out_" + t + ("" if sub is None else "_" + sub)] = vv
+    k = max(1, DUMP_OUT_ELEMS // max(1, len(flat)))
+    return {n: _sample(v, k, n) for n, v in flat.items()}
+
+
+def write_dump(path, outs, loss, model):
+    """--dump-outputs: the sampled outputs of the last timed step, its loss and a seeded sample of the parameters it left behind"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    params = list(model.named_parameters())
+    k = max(1, min(4096, DUMP_PARAM_ELEMS // max(1, len(params))))
+    arrays = {n: v.cpu().numpy() for n, v in outs.items()}
+    arrays["loss"] = np.array([float(loss.detach())], np.float64)
+    arrays["params"] = torch.cat([_sample(v, k, n) for n, v in params]).cpu().numpy()
+    for n, v in arrays.items():
+        np.save(os.path.join(path, n + ".npy"), v)
+
+
 MODE_DTYPE = {
     "bf16": "bf16",
     "x3f": "f32(bf16x3)",
@@ -560,6 +616,8 @@ def main():
     if "RANK" in os.environ and a.gpus != world and rank == 0:
         print(f"bench.py: --gpus {a.gpus} but WORLD_SIZE={world}: the launcher's world size is what runs and what n_gpus reports", file=sys.stderr)
     on_gpu = a.device == "cuda"
+    if not a.full:                        # a plain run: set-up, warm-up, the timed steps, the line
+        a.no_fwd = a.no_roofline = a.no_parity = a.no_ref_batch = a.no_torch_baseline = a.no_cpu_baseline = a.no_fast_mode = a.no_x3_mode = True
     if on_gpu:
         torch.cuda.set_device(local)
         dev = torch.device("cuda", local)
@@ -650,8 +708,10 @@ def main():
         gt = mtt_amd.losses.synthetic_targets(p, bsz, H, W, dev, seed=rank)
 
         def make_step(xb, gtb):
-            def step():
+            def step(keep=None):
                 out = net(xb)
+                if keep is not None:                              # --dump-outputs: sample the task outputs before the loss sees them
+                    keep.update(_sample_outputs(out))
                 loss = crit(out, gtb)["total"]
                 opt.zero_grad(set_to_none=True)
                 loss.backward()
@@ -667,9 +727,10 @@ def main():
         if world > 1 and headline:
             dist.barrier()
         torch.cuda.synchronize()
+        dumped = {} if (a.dump_outputs and headline and rank == 0) else None
         t0 = time.perf_counter()
-        for _ in range(a.steps):
-            loss = step()
+        for i in range(a.steps):
+            loss = step(dumped if i == a.steps - 1 else None)
         torch.cuda.synchronize()
         if world > 1 and headline:
             dist.barrier()
@@ -682,6 +743,8 @@ def main():
         rec = dict(mode=prec, dtype=MODE_DTYPE[prec], arithmetic=MODE_TEXT[prec], ms_per_step=dt / a.steps * 1e3,
                    images_per_s=bsz * (world if headline else 1) * a.steps / dt, steps=a.steps, warmup=a.warmup, per_gpu_batch=bsz,
                    loss=float(loss.detach()), peak_hbm_gb=round(torch.cuda.max_memory_allocated() / 2**30, 1), tasks=list(p.TASKS.NAMES))
+        if dumped is not None:
+            write_dump(a.dump_outputs, dumped, loss, model)
 
         def host_share(fn):
             """host time to ENQUEUE one step (python + ctypes + launches, no sync) against the step's wall time: far below 1 = GPU-bound."""
@@ -693,7 +756,7 @@ def main():
             h2 = time.perf_counter()
             return dict(enqueue_ms=round((h1 - h0) * 1e3, 2), step_ms=round((h2 - h0) * 1e3, 2))
 
-        rec["host"] = host_share(step)
+        rec["host"] = host_share(step) if a.full else None
 
         # forward-only latency (the metric's second half), same process
         rec["fwd_ms_per_img"] = None

@@ -209,12 +209,32 @@ def test_bench_gpus_flag_launches_that_many_ranks():
     assert abs(two["config"]["loss"] - one["config"]["loss"]) < 0.5 * abs(one["config"]["loss"])
 
 
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A run without --full times exactly --steps steps and leaves every other record null; --dump-outputs writes the last timed step's
+    sampled task outputs, loss and parameters as float32 / float64 .npy files that two runs with the same arguments reproduce bit for bit."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = _run_bench_emulated("--gpus", "1", "--dump-outputs", str(d))
+        assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["unit"] == "images/s"
+        assert all(r[k] is None for k in ("host", "fwd_ms_per_img", "roofline", "parity", "fast_mode", "full_fp32_mode", "ref_batch",
+                                          "torch_rocm_baseline", "cpu_baseline"))
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    names = set(dumps[0])
+    assert {"loss.npy", "params.npy", "out_semseg.npy", "out_depth.npy"} <= names and names == set(dumps[1])
+    assert sum(v.nbytes for v in dumps[0].values()) <= 64 << 20
+    for n in names:
+        assert dumps[0][n].dtype in (np.float32, np.float64) and np.isfinite(dumps[0][n]).all(), n
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
 def test_bench_gpus_8_every_rank_takes_the_instrumented_step():
     """The driver's 8-GPU form `bench.py --gpus 8` end to end on the host: 8 gloo ranks on the CPU emulator, the
     instrumented roofline step kept (`--cpu-roofline`: wall-clock stamps instead of HIP events) so that every rank runs what it runs on the
     node — ranks != 0 take the extra step too, because under DDP its gradient all-reduce is a collective (a rank that skipped it would
     hang the others).  ONE line, from rank 0: n_gpus 8, dp8, global batch = 8 x per-GPU batch, whole-job throughput, a roofline record."""
-    r = _run_bench_emulated("--gpus", "8", "--cpu-roofline", timeout=1500)
+    r = _run_bench_emulated("--gpus", "8", "--cpu-roofline", "--full", timeout=1500)
     assert r["n_gpus"] == 8 and r["config"]["gloo_ranks"] == 8 and r["config"]["parallelism"] == "dp8"
     assert r["config"]["global_batch"] == 8 * r["config"]["per_gpu_batch"] and r["scaling"] == "weak"
     assert abs(r["value"] - r["config"]["global_batch"] / (r["ms_per_step"] * 1e-3)) < 1e-2 * r["value"]
