@@ -614,8 +614,9 @@ def linear(x, wpack, N, prec, *, bias=None, act=ACT_NONE, out=None, out_dtype=No
 
 def head_prologue_ok(rows, K, n, lda):
     """can mtt_gemm apply BatchNorm + activation while loading the A operand (mtt_gemm_desc.a_scale)?  Only its exact-fp32 tall kernel does
-    (gemm_f32n_kernel: fp32 operands, at most 32 outputs, K <= 1024 in whole 8-chunks; with a prologue it takes any row count)."""
-    return n <= 32 and K % 8 == 0 and K <= 1024 and rows >= 1 and lda % 4 == 0
+    (gemm_f32n_kernel: fp32 operands, at most 32 outputs, K <= 1024 in whole 8-chunks; with a prologue it takes any row count).  That kernel
+    is chosen under MTT_GEMM_AUTO only: with the GEMM_VARIANT hook set, call() would force another kernel and mtt_gemm refuses the prologue."""
+    return GEMM_VARIANT is None and n <= 32 and K % 8 == 0 and K <= 1024 and rows >= 1 and lda % 4 == 0
 
 
 SPLIT_CONV_MAX_ELEMS = 2 ** 31 - 1          # gemm_variant_for: (int64) M * lda < 2^31 for variant 9 (tests lower it to force chunks)

@@ -12,6 +12,7 @@ import math
 import torch
 
 F32, BF16, SPLIT = 0, 1, 2        # SPLIT: x = hi + lo, two bf16 planes (main pointer = hi, *_lo = lo)
+ATTN_PLAIN = 1                     # mtt_attn_desc.variant: the plain (non-flash) kernel
 OP_K, OP_R, OP_CONV_K, OP_CONV_R = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_GELU_BWD, ACT_RELU_BWD, ACT_GELU_DAUX, ACT_MUL_AUX = 0, 1, 2, 3, 4, 5, 6
 
@@ -211,7 +212,23 @@ def attn_fwd(**kw):
     s = raw * kw["scale"]
     if kw.get("lse") is not None:
         _wr(kw["lse"], torch.arange(B * nH * N), torch.logsumexp(s, dim=-1).reshape(-1))
-    y = (torch.softmax(s, dim=-1) @ v).transpose(1, 2).reshape(-1)
+    if kw.get("prec", 0) == 0 and kw.get("dtype") == BF16 and kw.get("variant", 0) != ATTN_PLAIN and out.data_ptr() % 16 == 0:
+        # the flash kernel (attn_fwd_fast_kernel): per 64-key tile p = exp(s - running max) in fp32, the row sum of the UNROUNDED p, and the
+        # PV product on bf16(p) — P itself is a bf16 MFMA operand; the output is acc / sum
+        m = torch.full(s.shape[:-1] + (1,), -math.inf, dtype=torch.float64)
+        l = torch.zeros_like(m)
+        acc = torch.zeros(s.shape[:-1] + (64,), dtype=torch.float64)
+        for j0 in range(0, N, 64):
+            sj = s[..., j0:j0 + 64]
+            m_new = torch.maximum(m, sj.amax(-1, keepdim=True))
+            alpha = torch.exp(m - m_new)
+            pj = torch.exp(sj - m_new)
+            l = l * alpha + pj.sum(-1, keepdim=True)
+            acc = acc * alpha + _bf16_round(pj) @ v[..., j0:j0 + 64, :]
+            m = m_new
+        y = (acc / l).transpose(1, 2).reshape(-1)
+    else:
+        y = (torch.softmax(s, dim=-1) @ v).transpose(1, 2).reshape(-1)
     _wr(out, torch.arange(B * N * C), y)
     if split:
         _wr(kw["out_lo"], torch.arange(B * N * C), y - _bf16_round(y))
@@ -227,13 +244,17 @@ def attn_bwd(**kw):
     g = _rd(dout, torch.arange(B * N * C)).view(B, N, nH, 64).transpose(1, 2)
     raw = q @ k.transpose(-1, -2)
     P = torch.softmax(raw * kw["scale"], dim=-1)
-    dV = P.transpose(-1, -2) @ g
     dP = g @ v.transpose(-1, -2)
-    D = (dP * P).sum(-1, keepdim=True)
-    dS = kw["scale"] * P * (dP - D)
+    # D = rowsum(dO * O) over the STORED (bf16) forward output, as attn_stat_kernel forms it (= rowsum(dP * P) up to that rounding)
+    O = _rd(kw["out"], torch.arange(B * N * C)).view(B, N, nH, 64).transpose(1, 2)
+    D = (g * O).sum(-1, keepdim=True)
+    # the kernels (attn_bwd_dq / dkv): P and dS / scale are bf16 MFMA operands of dV = P^T dO, dQ = dS K, dK = dS^T Q
+    dS = P * (dP - D)
     if drawlog is not None and T > 0:
-        dS[:, :, :T] += _rd(drawlog, torch.arange(B * nH * T * N)).view(B, nH, T, N)
-    dQ, dK = dS @ k, dS.transpose(-1, -2) @ q
+        dS[:, :, :T] += _rd(drawlog, torch.arange(B * nH * T * N)).view(B, nH, T, N) / kw["scale"]
+    P16, dS16 = _bf16_round(P), _bf16_round(dS)
+    dV = P16.transpose(-1, -2) @ g
+    dQ, dK = kw["scale"] * (dS16 @ k), kw["scale"] * (dS16.transpose(-1, -2) @ q)
     out = torch.stack([dQ, dK, dV], 0).permute(1, 3, 0, 2, 4).reshape(-1)      # [B, N, 3, nH, 64]
     _wr(dqkv, torch.arange(B * N * 3 * C), out)
     Np = (N + 3) // 4 * 4
