@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTT_ABI_VERSION 13
+#define MTT_ABI_VERSION 14
 
 /* MTT_SPLIT: an fp32-class value stored as TWO bf16 planes of identical layout, x = hi + lo with hi = bf16(x), lo = bf16(x - hi)
  * (~16 mantissa bits).  The main pointer of an operand addresses the hi plane, its `*_lo` companion the lo plane.  The hi plane alone is
@@ -139,7 +139,7 @@ size_t mtt_gemm_colsum_ws_floats(const mtt_gemm_desc* d);
 
 int mtt_abi_version(void);
 /* sizeof(descriptor): 0 gemm, 1 attn, 2 softmax, 3 ln, 4 chanlogit, 5 modulate, 6 ctr, 7 resize, 8 bn, 9 conv_geom, (15 adam, 16 loss, 17 upconv, 18 gather, 19 winattn, 20 chanattn, 21 conv3s2)
- * 10 dwconv, 11 pool, 12 lnmt, 13 attnmsg, 14 convt, 17 upconv */
+ * 10 dwconv, 11 pool, 12 lnmt, 13 attnmsg, 14 convt, 17 upconv, 22 segcopy, 23 ctrw, 24 detloss (ABI 14's: mtt_det_desc_size) */
 size_t mtt_desc_size(int which);
 int mtt_gemm(const mtt_gemm_desc* d, void* stream);
 /* which kernel mtt_gemm dispatches this descriptor to: 0 register-staged 128x128 (general), 3 phased LDS-DMA 256x256
@@ -564,6 +564,90 @@ int mtt_conv3s2_nchw_bwd(const mtt_conv3s2_desc* d, const float* dy, float* dx, 
 int mtt_boxes_overlap_bev(const float* boxes_a, int na, const float* boxes_b, int nb, float* out, int iou, void* stream);
 size_t mtt_nms_ws_bytes(int n);
 int mtt_nms_bev(const float* boxes, int n, float thresh, int rotated, long long* keep, int* num_out, void* ws, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * ABI 14 — the FCOS3D detection head and its FPN neck (the 3ddet task: TaskPrompter/detection_toolbox/det_head.py, fpn.py; the
+ * mmcv 1.6.2 layers they build through ConvModule).  All four families below are new entry points; no earlier struct changed.
+ *
+ * GroupNorm (+ ReLU) on NHWC rows (ConvModule's 'gn' + 'activate', det_head.py:208-216,238-246; nn.GroupNorm semantics):
+ *   x (x_dtype) [Z*B*HW rows, ld]: Z stacked layers of B images of HW pixels, C valid channels in G groups of C/G channels.
+ *   Statistics per (z, image, group) over HW*C/G values, biased variance; mean / rstd fp32 [Z*B*G] are written by the forward.
+ *   y = act((x - mean) * rstd * gamma[z*C + c] + beta[z*C + c]); act = ReLU when relu != 0.  y (y_dtype: F32 / BF16 / SPLIT with the lo
+ *   plane at y_lo) has pitch ld; channels C..ld-1 are written as zeros.  G may be large (a batch of branch layers as ONE GroupNorm).
+ *   bwd: dy (dy_dtype, pitch ld) -> dx (dx_dtype, pitch ld, padding written as zeros), dgamma / dbeta fp32 [Z*C] (written); reads x,
+ *   mean, rstd, gamma, beta of the forward (the ReLU mask is recomputed).
+ *   Both directions reduce through per-workgroup partials in ws (>= mtt_groupnorm_ws_floats(d) floats), summed in a fixed order. */
+/* sizeof() of the ABI 14 descriptors: 0 gn, 1 dcn, 2 nearest, 3 bboxpost (0 otherwise) */
+size_t mtt_det_desc_size(int which);
+
+typedef struct {
+  const void* x; void* y; void* y_lo; const float* gamma; const float* beta; float* mean; float* rstd;
+  const void* dy; void* dx; float* dgamma; float* dbeta;
+  int32_t Z, B; int64_t HW; int32_t C, G; int64_t ld;
+  int32_t x_dtype, y_dtype, dy_dtype, dx_dtype;
+  int32_t relu; float eps;
+  float* ws;
+} mtt_gn_desc;
+size_t mtt_groupnorm_ws_floats(const mtt_gn_desc* d);
+int mtt_groupnorm_fwd(const mtt_gn_desc* d, void* stream);
+int mtt_groupnorm_bwd(const mtt_gn_desc* d, void* stream);
+
+/* Modulated deformable 3x3 convolution (DCNv2), the columns half: ModulatedDeformConv2dPack of mmcv 1.6.2 with deform_groups = groups = 1,
+ * selected by dcn_on_last_conv (det_head.py:225-226,248-249).  Sampling, restated from mmcv's modulated_deform_conv kernels:
+ *   tap k = i*3 + j of output pixel (ho, wo): h = ho*stride - pad + i*dil + dh_k,  w = wo*stride - pad + j*dil + dw_k
+ *   dh_k = offset[row, 2k], dw_k = offset[row, 2k+1]  (offset NULL: 0);  m_k = mask[row, k] (sigmoid of it when mask_sigmoid; NULL: 1)
+ *   value = 0 when h <= -1 || w <= -1 || h >= H || w >= W; otherwise the bilinear sample of the four corners around (h, w), corners
+ *   outside [0, H-1] x [0, W-1] contributing 0.  col[row, k*Cp + c] = m_k * value   (row = (b*Ho + ho)*Wo + wo, c < Cp).
+ *   x (x_dtype) NHWC [B*H*W, ldx] (channels C..Cp-1 zero); col (col_dtype F32 / BF16 / SPLIT with col_lo) [B*Ho*Wo, ldc >= 9*Cp].
+ * The convolution itself is mtt_gemm on col with the pack of mtt_gemm's implicit 3x3 conv (k = tap*Cp + ci).  With offset = mask = NULL
+ * this is a plain strided im2col (the FPN's stride-2 extra conv, fpn.py add_extra_convs='on_output').
+ * mtt_dcn_col2im_bwd: dcol (dcol_dtype, pitch ldc) -> dx (dx_dtype, pitch ldx, channels < Cp written) = the transpose of the sampling;
+ *   doffset / dmask (optional, off_dtype, layouts of offset / mask; dmask is the gradient of the mask LOGIT when mask_sigmoid).  dx is a
+ *   gather, no floating-point atomics: the samples are bucketed by their floor cell with a stable radix sort (integer keys, sample order
+ *   within a bucket) in ws (>= mtt_dcn_col2im_ws_floats(d) floats), then each input pixel sums its four neighbouring buckets in a fixed
+ *   order.  Bitwise reproducible run to run. */
+typedef struct {
+  const void* x; int32_t x_dtype; int64_t ldx;
+  const void* offset; int64_t ld_off;
+  const void* mask; int64_t ld_mask; int32_t mask_sigmoid; int32_t off_dtype;   /* offset / mask / doffset / dmask: F32 or BF16 */
+  void* col; void* col_lo; int32_t col_dtype; int64_t ldc;
+  int32_t B, H, W, C, Cp, Ho, Wo, stride, pad, dil;
+  const void* dcol; int32_t dcol_dtype;
+  void* dx; int32_t dx_dtype;
+  void* doffset; void* dmask;
+  void* ws;
+} mtt_dcn_desc;
+size_t mtt_dcn_col2im_ws_floats(const mtt_dcn_desc* d);
+int mtt_dcn_im2col(const mtt_dcn_desc* d, void* stream);
+int mtt_dcn_col2im_bwd(const mtt_dcn_desc* d, void* stream);
+
+/* FPN top-down step on NHWC maps (fpn.py: laterals[i-1] += F.interpolate(laterals[i], size=prev_shape, mode='nearest')):
+ *   out[b, y, x, c] = a[b, y, x, c] + src[b, iy(y), ix(x), c] for c < C (out may alias a), with torch's nearest index rule
+ *   iy = min(floor(y * (float)Hi / Ho), Hi - 1) (likewise ix) — any ratio, including 1.  dtype (F32 / BF16) for all three maps.
+ * mtt_nearest_add_bwd: a = the gradient of out [B, Ho, Wo] -> out = the gradient of src [B, Hi, Wi] (written, c < C): every coarse pixel
+ *   gathers the fine pixels that read it, in row-major order (the gradient of a is a itself). */
+typedef struct {
+  const void* a; const void* src; void* out;
+  int32_t B, C, Ho, Wo, Hi, Wi; int64_t ld_a, ld_src, ld_out; int32_t dtype;
+} mtt_nearest_desc;
+int mtt_nearest_add(const mtt_nearest_desc* d, void* stream);
+int mtt_nearest_add_bwd(const mtt_nearest_desc* d, void* stream);
+
+/* Per-level tail of FCOS3DHead.forward_single (det_head.py:440-457) and the NHWC -> NCHW store of the head outputs:
+ *   input channel j (0 <= j < nch = sum dims) is column j - (start of its group) of group g: x[g] fp32 [B*H*W, ldx[g]] (ngroups <= 8)
+ *   out fp32 NCHW [B, nch, H, W].  scales == NULL: out = x (a layout change).  scales fp32 [4] = (offset, depth, size, bbox2d):
+ *     j < 2: s0*x;  j == 2: exp(s1*x);  3 <= j < 6: exp(s2*x) + 1e-6;  last 4 channels when bbox2d: relu(s3*x);  others: x.
+ * mtt_fcos_bbox_post_bwd: dout (layout of out) -> dx[g] (layout of x[g]; columns dims[g]..ldx[g]-1 written as zeros) and, with scales,
+ *   dscales fp32 [4] (written), reduced through per-workgroup partials in ws (>= mtt_fcos_bbox_post_ws_floats(d) floats), fixed order. */
+typedef struct {
+  const float* x[8]; int64_t ldx[8]; int32_t dims[8]; int32_t ngroups;
+  float* out; const float* scales; int32_t bbox2d;
+  int32_t B, H, W;
+  const float* dout; float* dx[8]; float* dscales; float* ws;
+} mtt_bboxpost_desc;
+size_t mtt_fcos_bbox_post_ws_floats(const mtt_bboxpost_desc* d);
+int mtt_fcos_bbox_post(const mtt_bboxpost_desc* d, void* stream);
+int mtt_fcos_bbox_post_bwd(const mtt_bboxpost_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

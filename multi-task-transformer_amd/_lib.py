@@ -16,7 +16,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmtt_hip.so")
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 F32, BF16, SPLIT = 0, 1, 2
 PREC_BF16, PREC_X3 = 0, 1
 OP_K, OP_R, OP_CONV_K, OP_CONV_R = 0, 1, 2, 3
@@ -186,6 +186,31 @@ class SegcopyDesc(C.Structure):
     _fields_ = [("table", ptr), ("chunk_seg", ptr), ("chunk_off", ptr), ("n_chunks", i32), ("src_base", i64), ("dst_base", i64)]
 
 
+class GnDesc(C.Structure):
+    _fields_ = [("x", ptr), ("y", ptr), ("y_lo", ptr), ("gamma", ptr), ("beta", ptr), ("mean", ptr), ("rstd", ptr),
+                ("dy", ptr), ("dx", ptr), ("dgamma", ptr), ("dbeta", ptr),
+                ("Z", i32), ("B", i32), ("HW", i64), ("C", i32), ("G", i32), ("ld", i64),
+                ("x_dtype", i32), ("y_dtype", i32), ("dy_dtype", i32), ("dx_dtype", i32), ("relu", i32), ("eps", f32), ("ws", ptr)]
+
+
+class DcnDesc(C.Structure):
+    _fields_ = [("x", ptr), ("x_dtype", i32), ("ldx", i64), ("offset", ptr), ("ld_off", i64), ("mask", ptr), ("ld_mask", i64), ("mask_sigmoid", i32), ("off_dtype", i32),
+                ("col", ptr), ("col_lo", ptr), ("col_dtype", i32), ("ldc", i64),
+                ("B", i32), ("H", i32), ("W", i32), ("C", i32), ("Cp", i32), ("Ho", i32), ("Wo", i32), ("stride", i32), ("pad", i32), ("dil", i32),
+                ("dcol", ptr), ("dcol_dtype", i32), ("dx", ptr), ("dx_dtype", i32), ("doffset", ptr), ("dmask", ptr), ("ws", ptr)]
+
+
+class NearestDesc(C.Structure):
+    _fields_ = [("a", ptr), ("src", ptr), ("out", ptr), ("B", i32), ("C", i32), ("Ho", i32), ("Wo", i32), ("Hi", i32), ("Wi", i32),
+                ("ld_a", i64), ("ld_src", i64), ("ld_out", i64), ("dtype", i32)]
+
+
+class BboxPostDesc(C.Structure):
+    _fields_ = [("x", ptr * 8), ("ldx", i64 * 8), ("dims", i32 * 8), ("ngroups", i32),
+                ("out", ptr), ("scales", ptr), ("bbox2d", i32), ("B", i32), ("H", i32), ("W", i32),
+                ("dout", ptr), ("dx", ptr * 8), ("dscales", ptr), ("ws", ptr)]
+
+
 # entry point -> (descriptor struct, size index in mtt_desc_size) ; None = positional-argument entry
 DESCS = {
     "loss_fwd": LossDesc,
@@ -199,10 +224,13 @@ DESCS = {
     "gather_rows": GatherDesc, "winattn_fwd": WinAttnDesc, "chanattn_fwd": ChanAttnDesc, "conv3s2_nchw": Conv3s2Desc,
     "segcopy": SegcopyDesc,
     "ctr_weights": CtrwDesc, "detloss_fwd": DetLossDesc,
+    "groupnorm_fwd": GnDesc, "groupnorm_bwd": GnDesc, "dcn_im2col": DcnDesc, "dcn_col2im_bwd": DcnDesc,
+    "nearest_add": NearestDesc, "nearest_add_bwd": NearestDesc, "fcos_bbox_post": BboxPostDesc, "fcos_bbox_post_bwd": BboxPostDesc,
 }
 _SIZE_INDEX = [GemmDesc, AttnDesc, SoftmaxDesc, LnDesc, ChanLogitDesc, ModulateDesc, CtrDesc, ResizeDesc, BnDesc, ConvGeom,
                DwconvDesc, PoolDesc, LnMtDesc, AttnMsgDesc, ConvtDesc, AdamDesc, LossDesc, UpconvDesc,
                GatherDesc, WinAttnDesc, ChanAttnDesc, Conv3s2Desc, SegcopyDesc, CtrwDesc, DetLossDesc]
+_DET_SIZE_INDEX = [GnDesc, DcnDesc, NearestDesc, BboxPostDesc]        # mtt_det_desc_size (ABI 14)
 POSITIONAL = {
     "patchify16": [ptr, ptr, C.c_int, C.c_int, C.c_int, C.c_int, ptr],
     "patchify": [ptr, ptr, C.c_int, C.c_int, C.c_int, C.c_int, i64, C.c_int, ptr],
@@ -243,8 +271,9 @@ DESC_EXTRA = {
 
 # workspace-size queries mtt_<entry>_ws_floats(const desc*) of the entry points whose cross-workgroup reductions go through caller-owned partials
 WS_QUERIES = {"gemm_colsum": GemmDesc, "chan_logits": ChanLogitDesc, "modulate_bwd": ModulateDesc, "ctr_dw": CtrDesc, "attn_msg_bwd": AttnMsgDesc, "loss": LossDesc,
-              "chanattn_bwd": ChanAttnDesc, "detloss": DetLossDesc}
-EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA)]
+              "chanattn_bwd": ChanAttnDesc, "detloss": DetLossDesc,
+              "groupnorm": GnDesc, "dcn_col2im": DcnDesc, "fcos_bbox_post": BboxPostDesc}
+EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA)]
 
 _lib = None
 
@@ -273,6 +302,11 @@ def load():
     for idx, st in enumerate(_SIZE_INDEX):
         if lib.mtt_desc_size(idx) != C.sizeof(st):
             raise RuntimeError(f"descriptor layout mismatch for {st.__name__}: C {lib.mtt_desc_size(idx)} vs ctypes {C.sizeof(st)}")
+    lib.mtt_det_desc_size.restype = C.c_size_t
+    lib.mtt_det_desc_size.argtypes = [C.c_int]
+    for idx, st in enumerate(_DET_SIZE_INDEX):
+        if lib.mtt_det_desc_size(idx) != C.sizeof(st):
+            raise RuntimeError(f"descriptor layout mismatch for {st.__name__}: C {lib.mtt_det_desc_size(idx)} vs ctypes {C.sizeof(st)}")
     for name, st in DESCS.items():
         fn = getattr(lib, "mtt_" + name)
         fn.restype = C.c_int
@@ -367,6 +401,10 @@ def call(name, **kw):
                 setattr(desc, k, _addr(v))
             elif v is None:
                 setattr(desc, k, None)
+            elif isinstance(v, (list, tuple)):
+                arr = getattr(desc, k)
+                for i, e in enumerate(v):
+                    arr[i] = _addr(e) if isinstance(e, torch.Tensor) else e
             else:
                 setattr(desc, k, v)
         rc = fn(C.byref(desc), *extra, _stream()) if extra is not None else fn(C.byref(desc), _stream())

@@ -83,10 +83,22 @@ def get_backbone(p):
     return backbone, p.final_embed_dim
 
 
+def _plain(d):
+    """edict2dict: nested config dicts as plain dicts (the head's constructor takes keyword arguments and dict options)"""
+    if isinstance(d, dict):
+        return {k: _plain(v) for k, v in d.items()}
+    return d
+
+
 def get_head(p, backbone_channels, task):
     from . import taskprompter as tp
     if task == '3ddet':
-        raise NotImplementedError('FCOS3D head depends on mmcv/mmdet3d (out of scope, SURVEY.md §2 #17)')
+        # TaskPrompter/utils/common_config.py:52-58: FCOS3DHead(**det_head_params) + init_weights(), here on the HIP kernels (det_head.py)
+        from . import det_head
+        head = det_head.FCOS3DHead(**_plain(p.det_head_params))
+        head.init_weights()
+        head.set_prec(p.get('mtt_prec', DEFAULT_PREC))
+        return head
     if p['head'] == 'conv':
         return tp.ConvHead(backbone_channels, p.TASKS.NUM_OUTPUT[task])
     if p['head'] == 'deconv':
@@ -122,6 +134,12 @@ def get_model(p):
         return invpt.TransformerNet(p, backbone, ch, heads)
     if p['model'] == 'TaskPrompter':
         from . import taskprompter as tp
+        if '3ddet' in p.TASKS.NAMES:
+            # the head itself is built by get_head; what is missing is the backbone side (the Swin task-feature code does not yet yield the
+            # per-level list a 3ddet task reads, taskprompter_swin.py:709-710,741,764 of the reference), so a model would build but not run
+            raise NotImplementedError("get_model: the '3ddet' task's backbone features are not wired yet; build the head with get_head(p, ch, "
+                                      "'3ddet') after setting p.det_head_params.neck_cfg.in_channels = [p.final_embed_dim] * 4 "
+                                      "(common_config.py:41,80-81)")
         backbone, ch = get_backbone(p)
         heads = torch.nn.ModuleDict({task: get_head(p, ch, task) for task in p.TASKS.NAMES})
         return tp.TaskPrompterWrapper(p, backbone, heads)
