@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTT_ABI_VERSION 14
+#define MTT_ABI_VERSION 15
 
 /* MTT_SPLIT: an fp32-class value stored as TWO bf16 planes of identical layout, x = hi + lo with hi = bf16(x), lo = bf16(x - hi)
  * (~16 mantissa bits).  The main pointer of an operand addresses the hi plane, its `*_lo` companion the lo plane.  The hi plane alone is
@@ -648,6 +648,53 @@ typedef struct {
 size_t mtt_fcos_bbox_post_ws_floats(const mtt_bboxpost_desc* d);
 int mtt_fcos_bbox_post(const mtt_bboxpost_desc* d, void* stream);
 int mtt_fcos_bbox_post_bwd(const mtt_bboxpost_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * ABI 15 — the FCOS3D criterion of the 3ddet task (TaskPrompter/detection_toolbox/det_model.py DetModel.loss, :253-481, with
+ * pred_bbox2d: 13 regression channels = offset 2, depth 1, size 3, rotation 3, bbox2d 4).  New entry points only.
+ *
+ * Points: level l has H[l] x W[l] points, p = y * W + x (row-major, levels concatenated: P points per image);
+ *   xs = (float)x * stride[l] + half[l],  ys = (float)y * stride[l] + half[l]   (half = fp32(stride // 2)).
+ * Ground truth: labelled image k (0 <= k < n_lab) owns gts [img[k], img[k] + img[n_lab + k]) of gts (fp32 records of 16:
+ *   x1 y1 x2 y2 (bbox_modal), label, cx cy depth (center_I), size_S[3], rotation_S[3], 2 unused); img[2 n_lab + k] = its batch index,
+ *   img[3 n_lab + b] = the labelled index of batch image b, or -1 when it is dropped (det_label_number == 0).
+ * Assignment (_get_target_single, :858-955), in fp32 in the reference's operation order (the source is built without FMA contraction):
+ *   inside the centre box when min(xs - (cx - radius[l]), ys - (cy - radius[l]), (cx + radius[l]) - xs, (cy + radius[l]) - ys) > 0,
+ *   in range when rr_lo[l] <= max(l, t, r, b) <= rr_hi[l]; dist = sqrt(dx*dx + dy*dy), 1e8 when either test fails; the smallest dist
+ *   wins, the FIRST gt on ties; 1e8 = background (label C).  target (n_lab, 13, P) = (dx / stride, dy / stride, depth, size, rotation,
+ *   l / stride, t / stride, r / stride, b / stride) of the selected gt (gt 0 for background; zeros for an image without gts);
+ *   centerness (n_lab, P) = exp(-ctr_alpha * sqrt(dx*dx + dy*dy) / (1.414f * radius[l])); label int32 (n_lab, P).
+ * mtt_fcos3d_targets: the assignment alone (the head maps may be NULL; ws is not used).
+ * mtt_fcos3d_loss_fwd: the assignment and, in the same pass, the loss sums of every labelled point, read from the head's NCHW fp32 maps
+ *   in place (cls [B, C, H, W], bbox [B, 13, H, W], dir [B, 6, H, W], ctr [B, 1, H, W] per level); per-workgroup partials in ws
+ *   (>= mtt_fcos3d_ws_floats(d) floats), then one workgroup sums them in workgroup order and writes out[9] = (loss_cls, loss_offset,
+ *   loss_depth, loss_size, loss_rotsin, loss_dir, loss_centerness, loss_bbox2d, loss_sum) and stats[2] = (num_pos, num_pos + n_lab):
+ *   cls = sigmoid focal / (num_pos + n_lab); smooth-L1 x code_weight (rotation as sin(p)cos(t) - cos(p)sin(t)), the three 2-way
+ *   softmax CEs on floor(limit_period(rot - dir_offset, 0, 2 pi) / pi) and the centerness BCE-with-logits over positives / num_pos; each
+ *   times its loss weight; every positive-only term 0 when num_pos == 0.  Nothing is read back to the host.
+ * mtt_fcos3d_loss_bwd: gout[9] = the upstream gradient of out (component i receives gout[i] + gout[8]) -> every element of dcls / dbbox /
+ *   ddir / dctr (layouts of the maps) is written: zeros for dropped images and, in the bbox / dir / ctr maps, for non-positive points.
+ *   Reads label / target / centerness / stats of the forward.  No atomics: bitwise reproducible. */
+#define MTT_FCOS3D_MAX_LEVELS 8
+typedef struct {
+  const float* cls[8]; const float* bbox[8]; const float* dir[8]; const float* ctr[8];
+  float* dcls[8]; float* dbbox[8]; float* ddir[8]; float* dctr[8];
+  int32_t H[8], W[8];
+  float stride[8], half[8], radius[8], rr_lo[8], rr_hi[8];
+  int32_t nlev, B, n_lab, C;
+  int64_t P;
+  const int32_t* img; const float* gts;
+  int32_t* label; float* target; float* centerness;
+  float* ws; float* out; float* stats; const float* gout;
+  float code_weight[13];
+  float loss_weight[5];            /* cls, bbox (offset / depth / size / rotsin), dir, centerness, bbox2d */
+  float gamma, alpha, beta, beta2d, ctr_alpha, dir_offset;
+} mtt_fcos3d_desc;
+size_t mtt_fcos3d_desc_size(void);
+size_t mtt_fcos3d_ws_floats(const mtt_fcos3d_desc* d);
+int mtt_fcos3d_targets(const mtt_fcos3d_desc* d, void* stream);
+int mtt_fcos3d_loss_fwd(const mtt_fcos3d_desc* d, void* stream);
+int mtt_fcos3d_loss_bwd(const mtt_fcos3d_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

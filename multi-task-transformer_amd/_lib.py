@@ -16,7 +16,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmtt_hip.so")
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 F32, BF16, SPLIT = 0, 1, 2
 PREC_BF16, PREC_X3 = 0, 1
 OP_K, OP_R, OP_CONV_K, OP_CONV_R = 0, 1, 2, 3
@@ -211,6 +211,18 @@ class BboxPostDesc(C.Structure):
                 ("dout", ptr), ("dx", ptr * 8), ("dscales", ptr), ("ws", ptr)]
 
 
+class Fcos3dDesc(C.Structure):
+    _fields_ = [("cls", ptr * 8), ("bbox", ptr * 8), ("dir", ptr * 8), ("ctr", ptr * 8),
+                ("dcls", ptr * 8), ("dbbox", ptr * 8), ("ddir", ptr * 8), ("dctr", ptr * 8),
+                ("H", i32 * 8), ("W", i32 * 8),
+                ("stride", f32 * 8), ("half", f32 * 8), ("radius", f32 * 8), ("rr_lo", f32 * 8), ("rr_hi", f32 * 8),
+                ("nlev", i32), ("B", i32), ("n_lab", i32), ("C", i32), ("P", i64),
+                ("img", ptr), ("gts", ptr), ("label", ptr), ("target", ptr), ("centerness", ptr),
+                ("ws", ptr), ("out", ptr), ("stats", ptr), ("gout", ptr),
+                ("code_weight", f32 * 13), ("loss_weight", f32 * 5),
+                ("gamma", f32), ("alpha", f32), ("beta", f32), ("beta2d", f32), ("ctr_alpha", f32), ("dir_offset", f32)]
+
+
 # entry point -> (descriptor struct, size index in mtt_desc_size) ; None = positional-argument entry
 DESCS = {
     "loss_fwd": LossDesc,
@@ -226,6 +238,7 @@ DESCS = {
     "ctr_weights": CtrwDesc, "detloss_fwd": DetLossDesc,
     "groupnorm_fwd": GnDesc, "groupnorm_bwd": GnDesc, "dcn_im2col": DcnDesc, "dcn_col2im_bwd": DcnDesc,
     "nearest_add": NearestDesc, "nearest_add_bwd": NearestDesc, "fcos_bbox_post": BboxPostDesc, "fcos_bbox_post_bwd": BboxPostDesc,
+    "fcos3d_targets": Fcos3dDesc, "fcos3d_loss_fwd": Fcos3dDesc, "fcos3d_loss_bwd": Fcos3dDesc,
 }
 _SIZE_INDEX = [GemmDesc, AttnDesc, SoftmaxDesc, LnDesc, ChanLogitDesc, ModulateDesc, CtrDesc, ResizeDesc, BnDesc, ConvGeom,
                DwconvDesc, PoolDesc, LnMtDesc, AttnMsgDesc, ConvtDesc, AdamDesc, LossDesc, UpconvDesc,
@@ -272,8 +285,8 @@ DESC_EXTRA = {
 # workspace-size queries mtt_<entry>_ws_floats(const desc*) of the entry points whose cross-workgroup reductions go through caller-owned partials
 WS_QUERIES = {"gemm_colsum": GemmDesc, "chan_logits": ChanLogitDesc, "modulate_bwd": ModulateDesc, "ctr_dw": CtrDesc, "attn_msg_bwd": AttnMsgDesc, "loss": LossDesc,
               "chanattn_bwd": ChanAttnDesc, "detloss": DetLossDesc,
-              "groupnorm": GnDesc, "dcn_col2im": DcnDesc, "fcos_bbox_post": BboxPostDesc}
-EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA)]
+              "groupnorm": GnDesc, "dcn_col2im": DcnDesc, "fcos_bbox_post": BboxPostDesc, "fcos3d": Fcos3dDesc}
+EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_fcos3d_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA)]
 
 _lib = None
 
@@ -307,6 +320,10 @@ def load():
     for idx, st in enumerate(_DET_SIZE_INDEX):
         if lib.mtt_det_desc_size(idx) != C.sizeof(st):
             raise RuntimeError(f"descriptor layout mismatch for {st.__name__}: C {lib.mtt_det_desc_size(idx)} vs ctypes {C.sizeof(st)}")
+    lib.mtt_fcos3d_desc_size.restype = C.c_size_t
+    lib.mtt_fcos3d_desc_size.argtypes = []
+    if lib.mtt_fcos3d_desc_size() != C.sizeof(Fcos3dDesc):                           # ABI 15
+        raise RuntimeError(f"descriptor layout mismatch for Fcos3dDesc: C {lib.mtt_fcos3d_desc_size()} vs ctypes {C.sizeof(Fcos3dDesc)}")
     for name, st in DESCS.items():
         fn = getattr(lib, "mtt_" + name)
         fn.restype = C.c_int

@@ -3,8 +3,9 @@ closed form and a reference host path to pin against: `FocalLoss` (sigmoid focal
 calls mmcv-full 1.6.2's `sigmoid_focal_loss` extension, on the host its own `py_sigmoid_focal_loss`, :183-224) and `SmoothL1Loss`
 (:102-181), with the reference's weighting / reduction rules (`weight_reduce_loss`, :28-54).  Same constructor and call signatures; the
 element-wise loss, its weighted sum and the gradient run on the HIP kernels mtt_detloss_fwd / mtt_detloss_bwd (deterministic sum, the
-upstream scalar read on the device: no host synchronisation).  The FCOS3D head and FPN that would feed them need mmcv / mmdet3d modules
-(DCN, ConvModule, bbox coders) that are absent from this image and have no oracle: DESIGN.md §13.  Raises on CPU tensors (no fallback)."""
+upstream scalar read on the device: no host synchronisation).  The FCOS3D head and FPN are det_head.py, pinned to the reference's own
+det_head.py / fpn.py (tests/golden/mini_det.*); the FCOS3D criterion (det_model.py) evaluates its focal and smooth-L1 terms in its own
+kernels and does not go through these classes.  Raises on CPU tensors (no fallback)."""
 import torch
 import torch.nn as nn
 

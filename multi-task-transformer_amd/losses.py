@@ -88,18 +88,35 @@ def _fused_spec(p, task):
 
 class FusedMultiTaskLoss(nn.Module):
     """loss_schemes.py:9-39 with the per-task losses of utils/common_config.py:200-228 on the HIP kernels (same call signature and
-    result dict as the reference's MultiTaskLoss)."""
+    result dict as the reference's MultiTaskLoss).  The '3ddet' task (TaskPrompter loss_schemes.py:19-36) takes its criterion from
+    p.detmodel (det_model.DetModel, e.g. set by det_model.configure_3ddet) and the whole gt dict: out['3ddet'] = loss_sum, the
+    component dict is merged into out, and weights['3ddet'] * loss_sum enters the total."""
 
     def __init__(self, p, tasks, loss_weights=None):
         super().__init__()
         self.tasks = list(tasks)
-        self.spec = {t: _fused_spec(p, t) for t in self.tasks}
-        self.loss_weights = dict(loss_weights or {t: DEFAULT_WEIGHTS[t] for t in self.tasks})
+        self.spec = {t: _fused_spec(p, t) for t in self.tasks if t != '3ddet'}
+        self.loss_weights = dict(loss_weights or {t: DEFAULT_WEIGHTS.get(t, 1.0 if t == '3ddet' else None) for t in self.tasks})
+        if None in self.loss_weights.values():
+            raise KeyError([t for t, w in self.loss_weights.items() if w is None])
         self.intermediate_supervision = _intermediate(p)
+        self.detmodel = None
+        if '3ddet' in self.tasks:
+            self.detmodel = p['detmodel'] if isinstance(p, dict) else p.detmodel
+            if self.intermediate_supervision:
+                raise NotImplementedError("intermediate supervision with the '3ddet' task")
 
     def forward(self, pred, gt, tasks=None):
-        return _scheme(lambda t, a, b: _TaskLossFn.apply(a, b, *self.spec[t]), tasks or self.tasks, self.tasks, self.loss_weights,
-                       pred, gt, self.intermediate_supervision)
+        tasks = tasks or self.tasks
+        if '3ddet' not in tasks:
+            return _scheme(lambda t, a, b: _TaskLossFn.apply(a, b, *self.spec[t]), tasks, self.tasks, self.loss_weights,
+                           pred, gt, self.intermediate_supervision)
+        out = {t: _TaskLossFn.apply(pred[t], gt[t], *self.spec[t]) for t in tasks if t != '3ddet'}
+        det_losses, det_loss_sum = self.detmodel.loss(pred['3ddet'], gt)
+        out['3ddet'] = det_loss_sum
+        out = {**out, **det_losses}
+        out['total'] = torch.sum(torch.stack([self.loss_weights[t] * out[t] for t in tasks]))
+        return out
 
 
 def synthetic_targets(p, B, H, W, device, seed=0):

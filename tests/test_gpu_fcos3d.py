@@ -1,0 +1,244 @@
+"""-m gpu: the FCOS3D criterion (det_model.DetModel, csrc/det_loss3d.hip) against the unmodified reference (tests/golden/fcos3d.*,
+make_fcos3d_golden.py) and the plain-torch restatement tests/fcos3d_ref.py: labels bit for bit, the eight components, loss_sum, every map
+gradient, the mini_det head chain, run-to-run bitwise reproducibility, no host synchronisation, FusedMultiTaskLoss with '3ddet', and
+the cs geometry."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import conftest
+import det_ref
+import fcos3d_ref
+import train_check
+from tests.golden import make_fcos3d_golden as mfg
+
+DEV = "cuda:0"
+
+
+def _need_gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+
+
+def _fixture():
+    with open(os.path.join(conftest.GOLDEN, "fcos3d.json")) as f:
+        meta = json.load(f)
+    return meta, np.load(os.path.join(conftest.GOLDEN, "fcos3d.npz"))
+
+
+def _crit(meta):
+    import mtt_amd
+    return mtt_amd.det_model.DetModel(**json.loads(json.dumps(meta["params"])))
+
+
+def _preds(arrs, name, L, requires_grad=True):
+    flat = [torch.from_numpy(arrs[f"{name}/pred{j}"]).to(DEV).requires_grad_(requires_grad) for j in range(4 * L)]
+    return flat, [flat[k * L:(k + 1) * L] for k in range(4)]
+
+
+def _rel(a, b):
+    return abs(a - b) / max(abs(b), 1e-30)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["a", "b", "d"])
+def test_targets_match_the_reference_fixture(name):
+    _need_gpu()
+    meta, arrs = _fixture()
+    c = meta["cases"][name]
+    crit = _crit(meta)
+    labels = mfg.load_labels(arrs, name, c["B"])
+    keep = [i for i in range(c["B"]) if int(labels["det_label_number"][i]) != 0]
+    dl = [labels["det_labels"][i] for i in keep]
+    pts = crit.get_points([tuple(l) for l in c["levels"]], torch.float32, DEV)
+    lab, tgt, ctr = crit.get_targets(pts, [e["bbox_modal"] for e in dl], [e["label"] for e in dl],
+                                     [torch.cat([e["center_S"], e["size_S"], e["rotation_S"]], 1) for e in dl], [e["label"] for e in dl],
+                                     [e["center_I"][:, :2] for e in dl], [e["center_I"][:, 2] for e in dl])
+    lab, tgt, ctr = torch.cat(lab).cpu(), torch.cat(tgt).cpu(), torch.cat(ctr).cpu()
+    ref = torch.from_numpy(arrs[f"{name}/labels"].astype(np.int64))
+    assert torch.equal(lab, ref), int((lab != ref).sum())
+    pos = lab < 6
+    assert int(pos.sum()) == c["num_pos"]
+    if name != "d":
+        rt, rc = torch.from_numpy(arrs[f"{name}/pos_targets"]), torch.from_numpy(arrs[f"{name}/pos_ctr"])
+        worst = lambda a, r: float(((a - r).abs() / r.abs().clamp(min=1e-6)).max()) if r.numel() else 0.0
+        assert worst(tgt[pos], rt) <= 1e-6 and worst(ctr[pos], rc) <= 1e-6
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["a", "b", "c"])
+def test_losses_and_gradients_match_the_reference_fixture(name):
+    _need_gpu()
+    meta, arrs = _fixture()
+    c = meta["cases"][name]
+    L = len(c["levels"])
+    crit = _crit(meta)
+    labels = mfg.load_labels(arrs, name, c["B"])
+    flat, preds = _preds(arrs, name, L)
+    ld, ls = crit.loss(preds, labels)
+    assert sorted(ld) == sorted(c["loss"])
+    for k, v in ld.items():
+        ref = c["loss"][k]
+        assert (float(v) == 0.0) if ref == 0.0 else _rel(float(v), ref) < 1e-5, (k, float(v), ref)
+    assert _rel(float(ls), c["loss_sum"]) < 1e-5 if c["loss_sum"] else float(ls) == 0.0
+    grads = torch.autograd.grad(ls, flat, retain_graph=bool(ld))
+    for j, g in enumerate(grads):
+        ref = torch.from_numpy(arrs[f"{name}/grad{j}"])
+        g = g.cpu()
+        assert float((g - ref).abs().max()) <= 1e-5 * max(float(ref.abs().max()), 1e-30), j
+        if name == "a":
+            assert not g[1].any(), "the unlabelled image must get zero gradient"
+        if name == "c" or (name == "b" and j >= L):
+            assert not g.any(), j
+    if name == "a":                                           # backprop of one component
+        grads = torch.autograd.grad(ld["loss_rotsin"], flat)
+        for j, g in enumerate(grads):
+            ref = torch.from_numpy(arrs[f"a/grad_rotsin{j}"])
+            assert float((g.cpu() - ref).abs().max()) <= 1e-5 * max(float(ref.abs().max()), 1e-30), j
+
+
+FIXTURE_GRAD_TOL = {"x3": 2.5e-2, "x3f": 0.15}                # the bounds test_gpu_det_head.py uses for the mini_det head
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", ["x3", "x3f", "bf16"])
+def test_mini_det_head_chain_matches_the_reference_fixture(prec):
+    """the HIP FCOS3DHead (mini_det weights and inputs) -> DetModel.loss -> backward, against the reference head + reference criterion:
+    the components, and per head parameter the norm and a fixed random projection of d loss_sum / d parameter"""
+    _need_gpu()
+    import mtt_amd
+    from tests.golden import make_det_golden as mdg
+    meta, arrs = _fixture()
+    c = meta["cases"]["d"]
+    _, harr = conftest.load_golden("mini_det")
+    torch.manual_seed(0)
+    head = mtt_amd.det_head.FCOS3DHead(**det_ref.mini_head_params())
+    head.init_weights()
+    det_ref.randomize(head, 0)
+    head.set_prec(prec)
+    head = head.to(DEV)
+    feats = [torch.from_numpy(np.asarray(harr[f"in{i}"])).to(DEV) for i in range(4)]
+    ld, ls = _crit(meta).loss(head(feats), mfg.load_labels(arrs, "d", c["B"]))
+    worst = max(_rel(float(v), c["loss"][k]) for k, v in ld.items())
+    ls.backward()
+    stats = mdg.grad_stats((k, p.grad.detach().cpu()) for k, p in head.named_parameters())
+    ref = {k: tuple(v) for k, v in c["grad_stats"].items()}
+    top = max(ref[k][0] / p.numel() ** 0.5 for k, p in head.named_parameters())
+    errs = {}
+    for k, p in head.named_parameters():
+        n_ref, pr_ref = ref[k]
+        if n_ref / p.numel() ** 0.5 < train_check.PER_PARAM["bf16"]["floor"] * top:
+            continue
+        n, pr = stats[k]
+        errs[k] = max(abs(n - n_ref), abs(pr - pr_ref)) / n_ref
+    wk = max(errs, key=errs.get)
+    print(f"mini_det head -> DetModel.loss {prec}: worst component rel err {worst:.3e}; {len(errs)} parameters, worst gradient error "
+          f"{errs[wk]:.3e} ({wk})")
+    if prec in FIXTURE_GRAD_TOL:
+        assert worst < 1e-3, worst
+        assert errs[wk] < FIXTURE_GRAD_TOL[prec], (wk, errs[wk])
+    else:
+        # bf16: measured and reported, bounded by direction (the cosine of the gradient projections over the checked parameters)
+        v = np.array([stats[k][1] for k in errs])
+        r = np.array([ref[k][1] for k in errs])
+        cos = float(v @ r / (np.linalg.norm(v) * np.linalg.norm(r)))
+        print(f"mini_det head -> DetModel.loss bf16: projection cosine {cos:.4f}")
+        assert cos > 0.8, cos
+
+
+CS_LEVELS = ((96, 192), (48, 96), (24, 48), (24, 48), (12, 24))
+
+
+def _cs_case(B, seed=0, n_gts=40):
+    import mtt_amd
+    dm = mtt_amd.det_model
+    p = {"IMAGE_ORI_SIZE": (1024, 2048), "TRAIN": {"SCALE": (1024, 2048)}, "img_ds_ratio": 0.75}
+    dm.configure_3ddet(p)
+    labels = dm.synthetic_det_labels(B, (1024, 2048), n_gts, seed=seed)
+    g = torch.Generator().manual_seed(seed + 1)
+    preds = [[(torch.randn(B, ch, h, w, generator=g) * (2.0 if k == 0 else 1.0)).to(DEV) for h, w in CS_LEVELS]
+             for k, ch in enumerate((6, 13, 6, 1))]
+    return p, labels, preds
+
+
+@pytest.mark.gpu
+def test_cs_geometry_matches_the_restatement():
+    """five levels 96x192 ... 12x24, strides [8, 16, 32, 32, 64] / 0.75, B = 2, 40 gts per image: labels identical to the fp32
+    restatement, components within 1e-5 of its fp64 losses"""
+    _need_gpu()
+    p, labels, preds = _cs_case(2)
+    crit = p["detmodel"]
+    ld, ls = crit.loss(preds, labels)
+    keep, lab, _, _ = fcos3d_ref.assign(p["det_model_params"], labels, CS_LEVELS)
+    pts = crit.get_points(CS_LEVELS, torch.float32, DEV)
+    dl = labels["det_labels"]
+    glab, _, _ = crit.get_targets(pts, [e["bbox_modal"] for e in dl], [e["label"] for e in dl],
+                                  [torch.cat([e["center_S"], e["size_S"], e["rotation_S"]], 1) for e in dl], [e["label"] for e in dl],
+                                  [e["center_I"][:, :2] for e in dl], [e["center_I"][:, 2] for e in dl])
+    offs = np.cumsum([0] + [h * w for h, w in CS_LEVELS])
+    ref = torch.cat([lab[:, offs[l]:offs[l + 1]].reshape(-1) for l in range(5)])
+    assert torch.equal(torch.cat(glab).cpu(), ref)
+    num_pos = int((ref < 6).sum())
+    assert num_pos > 100
+    rd, rs = fcos3d_ref.loss(p["det_model_params"], [[m.cpu() for m in lst] for lst in preds], labels)
+    for k in rd:
+        assert _rel(float(ld[k]), float(rd[k])) < 1e-5, (k, float(ld[k]), float(rd[k]))
+    assert _rel(float(ls), float(rs)) < 1e-5
+    print(f"cs geometry B=2: num_pos {num_pos}, " + ", ".join(f"{k} {float(v):.4f}" for k, v in ld.items()))
+
+
+@pytest.mark.gpu
+def test_two_runs_are_bitwise_equal():
+    _need_gpu()
+    p, labels, preds = _cs_case(2, seed=4)
+    runs = []
+    for _ in range(2):
+        leaves = [[m.clone().requires_grad_(True) for m in lst] for lst in preds]
+        ld, ls = p["detmodel"].loss(leaves, labels)
+        ls.backward()
+        runs.append([torch.stack(list(ld.values())), ls.detach()] + [m.grad.clone() for lst in leaves for m in lst])
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+def test_forward_and_backward_do_not_synchronise_with_the_host():
+    _need_gpu()
+    p, labels, preds = _cs_case(2, seed=5)
+    crit = p["detmodel"]
+    leaves = [[m.clone().requires_grad_(True) for m in lst] for lst in preds]
+    packed = crit.pack_labels(labels, DEV)
+    crit.loss(leaves, packed)[1].backward()              # warm-up: the kernel workspace is sized outside the checked region
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        ld, ls = crit.loss(leaves, packed)
+        ls.backward()
+    finally:
+        torch.cuda.set_sync_debug_mode(0)
+    assert torch.isfinite(ls).item()
+
+
+@pytest.mark.gpu
+def test_fused_multitask_loss_with_3ddet():
+    """['semseg', 'depth', '3ddet'] with weights {100, 1, 1}: the reference scheme's keys (loss_schemes.py:27-39) and total = the
+    weighted sum"""
+    _need_gpu()
+    import mtt_amd
+    p, labels, preds = _cs_case(1, seed=6)
+    P = mtt_amd.factory.AttrDict(ignore_index=255, detmodel=p["detmodel"], TASKS=dict(NAMES=['semseg', 'depth'], NUM_OUTPUT=dict(semseg=19, depth=1)))
+    crit = mtt_amd.losses.FusedMultiTaskLoss(P, ['semseg', 'depth', '3ddet'], {'semseg': 100.0, 'depth': 1.0, '3ddet': 1.0})
+    gt = mtt_amd.losses.synthetic_targets(P, 1, 32, 64, DEV)
+    gt.update(labels)
+    pred = {'semseg': torch.randn(1, 19, 32, 64, device=DEV), 'depth': torch.rand(1, 1, 32, 64, device=DEV) * 5, '3ddet': preds}
+    out = crit(pred, gt)
+    keys = ['semseg', 'depth', '3ddet', 'loss_cls', 'loss_offset', 'loss_depth', 'loss_size', 'loss_rotsin', 'loss_dir', 'loss_centerness',
+            'loss_bbox2d', 'total']
+    assert list(out) == keys
+    want = 100.0 * float(out['semseg']) + float(out['depth']) + float(out['3ddet'])
+    assert _rel(float(out['total']), want) < 1e-6
+    ld, ls = p["detmodel"].loss(preds, labels)
+    assert float(out['3ddet']) == float(ls)
