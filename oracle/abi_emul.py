@@ -7,6 +7,7 @@ ops in tests/test_abi_emul.py, then used (a) as the per-entry-point oracle of th
 tests and (b) monkeypatched over `_lib.call` by CPU tests to exercise the product's host-side wiring
 (descriptor construction, strides, padding) without a GPU.  Never imported by the product.
 """
+import contextlib
 import math
 
 import torch
@@ -36,9 +37,29 @@ def _rd(t, idx, valid=None):
     return v
 
 
+_WRITTEN = None      # {untyped storage data_ptr: bool mask over the storage} while a `tracking()` block is open
+
+
+@contextlib.contextmanager
+def tracking():
+    """Record the storage positions `_wr` writes: yields a dict {t.untyped_storage().data_ptr(): bool mask over the whole storage}
+    filled by the emulator calls inside the block (the raw-pointer writers segcopy / adam_step are not tracked).  Values are unchanged."""
+    global _WRITTEN
+    prev, _WRITTEN = _WRITTEN, {}
+    try:
+        yield _WRITTEN
+    finally:
+        _WRITTEN = prev
+
+
 def _wr(t, idx, val):
     f, o = flat(t)
     f[idx + o] = val.to(t.dtype)
+    if _WRITTEN is not None:
+        key = t.untyped_storage().data_ptr()
+        if key not in _WRITTEN:
+            _WRITTEN[key] = torch.zeros(f.numel(), dtype=torch.bool)
+        _WRITTEN[key][idx + o] = True
 
 
 def _rowoff(m, mb, bs, ld):

@@ -1,4 +1,5 @@
-"""-m gpu: every C-ABI entry point of libmtt_hip.so vs the CPU emulator (bit-for-bit identical inputs)."""
+"""-m gpu: the C-ABI entry points of libmtt_hip.so vs the CPU emulator (bit-for-bit identical inputs), every case of
+gpu_cases.all_cases(); the entry points without a case are checked by the tests gpu_cases.COVERED_ELSEWHERE names."""
 import pytest
 import torch
 

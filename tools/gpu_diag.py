@@ -25,7 +25,7 @@ def main():
         try:
             r = gpu_cases.run_case(entry, kw, None, tol)
             report[cname] = r
-            print(("PASS " if r["ok"] else "FAIL ") + cname, {k: (f"{v[0]:.2e}", f"{v[1]:.2e}") if isinstance(v, tuple) else v for k, v in r["errs"].items()}, flush=True)
+            print(("PASS " if r["ok"] else "FAIL ") + cname, {k: tuple(f"{x:.2e}" if isinstance(x, float) else x for x in v) if isinstance(v, tuple) else v for k, v in r["errs"].items()}, flush=True)
         except Exception as e:  # noqa: BLE001
             report[cname] = dict(ok=False, exc=repr(e))
             print("EXC  " + cname, repr(e), flush=True)
