@@ -1240,6 +1240,248 @@ def nms_bev(args):
     _wr(num_out, torch.arange(1), torch.tensor([len(k)]))
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# ABI 14: GroupNorm (+ReLU), modulated deformable im2col / col2im, the FPN's nearest add, the FCOS3D bbox tail.  Values in fp64; the
+# decisions that are discrete in the kernels (DCN sample cell, backward ReLU gate, nearest source index) in fp32 exactly as they take them.
+def _wr_any(t, t_lo, idx, v, dtype):
+    """Store v as `dtype`; SPLIT: hi = bf16(v) at t, lo = bf16(v - hi) at t_lo."""
+    if dtype == SPLIT:
+        hi = _bf16_round(v)
+        _wr(t, idx, hi)
+        _wr(t_lo, idx, v - hi)
+    else:
+        _wr(t, idx, v)
+
+
+def _gn_geom(kw):
+    Z, B, HW, C, G, ld = (int(kw[k]) for k in ("Z", "B", "HW", "C", "G", "ld"))
+    N = Z * B
+    idx = torch.arange(N * HW)[:, None] * ld + torch.arange(C)[None, :]                     # [rows, C]
+    pad = (torch.arange(N * HW)[:, None] * ld + torch.arange(C, ld)[None, :]).reshape(-1)   # channels C..ld-1
+    gamma = _rd(kw["gamma"], torch.arange(Z * C)).view(Z, 1, 1, C).expand(Z, B, 1, C).reshape(N, 1, C)
+    beta = _rd(kw["beta"], torch.arange(Z * C)).view(Z, 1, 1, C).expand(Z, B, 1, C).reshape(N, 1, C)
+    return Z, B, HW, C, G, N, idx, pad, gamma, beta
+
+
+def groupnorm_fwd(**kw):
+    Z, B, HW, C, G, N, idx, pad, gamma, beta = _gn_geom(kw)
+    cpg = C // G
+    x = _rd(kw["x"], idx).view(N, HW, G, cpg)
+    mean = x.mean((1, 3), keepdim=True)
+    var = (x - mean).square().mean((1, 3), keepdim=True)
+    rstd = (var + float(torch.tensor(kw["eps"], dtype=torch.float32))).rsqrt()
+    y = ((x - mean) * rstd).view(N, HW, C) * gamma + beta
+    if kw.get("relu"):
+        y = y.clamp_min(0.0)
+    yd = kw.get("y_dtype") or 0
+    _wr_any(kw["y"], kw.get("y_lo"), idx.reshape(-1), y.reshape(-1), yd)
+    _wr_any(kw["y"], kw.get("y_lo"), pad, torch.zeros(pad.numel(), dtype=torch.float64), yd)
+    _wr(kw["mean"], torch.arange(N * G), mean.reshape(-1))
+    _wr(kw["rstd"], torch.arange(N * G), rstd.reshape(-1))
+
+
+def groupnorm_bwd(**kw):
+    Z, B, HW, C, G, N, idx, pad, gamma, beta = _gn_geom(kw)
+    cpg = C // G
+    x = _rd(kw["x"], idx).view(N, HW, C)
+    dy = _rd(kw["dy"], idx).view(N, HW, C)
+    mean = _rd(kw["mean"], torch.arange(N * G)).view(N, 1, G, 1).expand(N, 1, G, cpg).reshape(N, 1, C)
+    rstd = _rd(kw["rstd"], torch.arange(N * G)).view(N, 1, G, 1).expand(N, 1, G, cpg).reshape(N, 1, C)
+    xh = (x - mean) * rstd
+    du = dy
+    if kw.get("relu"):
+        # the recomputed mask: xhat in fp32 from the stored statistics (a subtraction and a product, each rounded once), then the sign of
+        # xhat * gamma + beta — exact in fp64 for fp32 factors, so it is the sign of the kernel's fused multiply-add
+        xh32 = ((x.float() - mean.float()) * rstd.float()).double()
+        du = torch.where(xh32 * gamma + beta <= 0, torch.zeros_like(dy), dy)
+    inv = 1.0 / (HW * cpg)
+    dg = (du * gamma).view(N, HW, G, cpg)
+    s1 = dg.sum((1, 3), keepdim=True) * inv
+    s2 = (dg * xh.view(N, HW, G, cpg)).sum((1, 3), keepdim=True) * inv
+    dx = rstd * (du * gamma - s1.expand(N, 1, G, cpg).reshape(N, 1, C) - xh * s2.expand(N, 1, G, cpg).reshape(N, 1, C))
+    _wr(kw["dx"], idx.reshape(-1), dx.reshape(-1))
+    _wr(kw["dx"], pad, torch.zeros(pad.numel(), dtype=torch.float64))
+    if kw.get("dgamma") is not None:
+        _wr(kw["dgamma"], torch.arange(Z * C), (du * xh).view(Z, B * HW, C).sum(1).reshape(-1))
+    if kw.get("dbeta") is not None:
+        _wr(kw["dbeta"], torch.arange(Z * C), du.reshape(Z, B * HW, C).sum(1).reshape(-1))
+
+
+def _dcn_samples(kw):
+    """Per (row, tap): image, fp32 position (the base and the offset added in fp32, one rounding: the kernel's value), the in-box test,
+    floor cell and fractions taken on it, the modulation."""
+    B, H, W, Ho, Wo, stride, pad, dil = (int(kw[k]) for k in ("B", "H", "W", "Ho", "Wo", "stride", "pad", "dil"))
+    rows = B * Ho * Wo
+    r = torch.arange(rows)[:, None]
+    k = torch.arange(9)[None, :]
+    pix = r % (Ho * Wo)
+    h = ((pix // Wo) * stride - pad + (k // 3) * dil).float()
+    w = ((pix % Wo) * stride - pad + (k % 3) * dil).float()
+    if kw.get("offset") is not None:
+        h = h + _rd(kw["offset"], r * kw["ld_off"] + 2 * k).float()
+        w = w + _rd(kw["offset"], r * kw["ld_off"] + 2 * k + 1).float()
+    m = torch.ones(rows, 9, dtype=torch.float64)
+    if kw.get("mask") is not None:
+        m = _rd(kw["mask"], r * kw["ld_mask"] + k)
+        if kw.get("mask_sigmoid"):
+            m = torch.sigmoid(m)
+    inside = (h > -1) & (w > -1) & (h < H) & (w < W)
+    hf, wf = torch.floor(h), torch.floor(w)
+    return dict(b=(r // (Ho * Wo)).expand(rows, 9), inside=inside, hl=hf.long(), wl=wf.long(), lh=(h - hf).double(), lw=(w - wf).double(), m=m,
+                rows=rows, r=r, k=k)
+
+
+def _dcn_corners(kw, s):
+    """The four corners of every sample: (pixel index into the NHWC input rows, valid, weight, d weight / dh, d weight / dw)."""
+    H, W = int(kw["H"]), int(kw["W"])
+    lh, lw = s["lh"], s["lw"]
+    uh, uw = 1.0 - lh, 1.0 - lw
+    out = []
+    for dy, dx, wt, gh, gw in ((0, 0, uh * uw, -uw, -uh), (0, 1, uh * lw, -lw, uh), (1, 0, lh * uw, uw, -lh), (1, 1, lh * lw, lw, lh)):
+        yy, xx = s["hl"] + dy, s["wl"] + dx
+        ok = s["inside"] & (yy >= 0) & (yy <= H - 1) & (xx >= 0) & (xx <= W - 1)
+        out.append(((s["b"] * H + yy) * W + xx, ok, wt, gh, gw))
+    return out
+
+
+def dcn_im2col(**kw):
+    Cp, ldx, ldc = int(kw["Cp"]), int(kw["ldx"]), int(kw["ldc"])
+    s = _dcn_samples(kw)
+    c = torch.arange(Cp)
+    val = torch.zeros(s["rows"], 9, Cp, dtype=torch.float64)
+    for p, ok, wt, _, _ in _dcn_corners(kw, s):
+        v = _rd(kw["x"], p[:, :, None] * ldx + c, ok[:, :, None].expand(-1, -1, Cp))
+        val = val + wt[:, :, None] * v
+    idx = s["r"][:, :, None] * ldc + s["k"][:, :, None] * Cp + c
+    _wr_any(kw["col"], kw.get("col_lo"), idx.reshape(-1), (val * s["m"][:, :, None]).reshape(-1), kw.get("col_dtype") or 0)
+
+
+def dcn_col2im_bwd(**kw):
+    B, H, W, C, Cp, ldx, ldc = (int(kw[k]) for k in ("B", "H", "W", "C", "Cp", "ldx", "ldc"))
+    s = _dcn_samples(kw)
+    rows = s["rows"]
+    c = torch.arange(Cp)
+    g = _rd(kw["dcol"], s["r"][:, :, None] * ldc + s["k"][:, :, None] * Cp + c)            # [rows, 9, Cp]
+    corners = _dcn_corners(kw, s)
+    if kw.get("dx") is not None:
+        acc = torch.zeros(B * H * W, Cp, dtype=torch.float64)
+        for p, ok, wt, _, _ in corners:
+            contrib = (wt * s["m"])[:, :, None] * g
+            acc.index_add_(0, p[ok], contrib[ok])
+        acc[:, C:] = 0.0
+        _wr(kw["dx"], (torch.arange(B * H * W)[:, None] * ldx + c).reshape(-1), acc.reshape(-1))
+    if kw.get("doffset") is not None or kw.get("dmask") is not None:
+        gm = torch.zeros(rows, 9, dtype=torch.float64)
+        gh, gw = torch.zeros_like(gm), torch.zeros_like(gm)
+        cc = torch.arange(C)
+        for p, ok, wt, dh, dw in corners:
+            v = _rd(kw["x"], p[:, :, None] * ldx + cc, ok[:, :, None].expand(-1, -1, C))
+            gv = (g[:, :, :C] * v).sum(-1)
+            gm, gh, gw = gm + wt * gv, gh + dh * gv, gw + dw * gv
+        ins = s["inside"].double()
+        if kw.get("doffset") is not None:
+            _wr(kw["doffset"], (s["r"] * kw["ld_off"] + 2 * s["k"]).reshape(-1), (gh * s["m"] * ins).reshape(-1))
+            _wr(kw["doffset"], (s["r"] * kw["ld_off"] + 2 * s["k"] + 1).reshape(-1), (gw * s["m"] * ins).reshape(-1))
+        if kw.get("dmask") is not None:
+            dm = gm * s["m"] * (1.0 - s["m"]) if kw.get("mask_sigmoid") else gm
+            _wr(kw["dmask"], (s["r"] * kw["ld_mask"] + s["k"]).reshape(-1), (dm * ins).reshape(-1))
+
+
+def _nearest_src(n_out, n_in):
+    """torch's nearest index for an explicit output size, in fp32 as the kernel: min(floor(o * (in / out)), in - 1)."""
+    scale = torch.tensor(float(n_in), dtype=torch.float32) / torch.tensor(float(n_out), dtype=torch.float32)
+    return torch.floor(torch.arange(n_out, dtype=torch.float32) * scale).long().clamp_max(n_in - 1)
+
+
+def _nearest_geom(kw):
+    B, C, Ho, Wo, Hi, Wi = (int(kw[k]) for k in ("B", "C", "Ho", "Wo", "Hi", "Wi"))
+    iy, ix = _nearest_src(Ho, Hi), _nearest_src(Wo, Wi)
+    b = torch.arange(B)[:, None, None]
+    fine = ((b * Ho + torch.arange(Ho)[None, :, None]) * Wo + torch.arange(Wo)[None, None, :]).reshape(-1)     # fine pixel rows
+    coarse = ((b * Hi + iy[None, :, None]) * Wi + ix[None, None, :]).reshape(-1)                                # the coarse row each reads
+    return B, C, Hi, Wi, fine, coarse, torch.arange(C)[None, :]
+
+
+def nearest_add(**kw):
+    B, C, Hi, Wi, fine, coarse, c = _nearest_geom(kw)
+    v = _rd(kw["a"], fine[:, None] * kw["ld_a"] + c) + _rd(kw["src"], coarse[:, None] * kw["ld_src"] + c)
+    _wr(kw["out"], (fine[:, None] * kw["ld_out"] + c).reshape(-1), v.reshape(-1))
+
+
+def nearest_add_bwd(**kw):
+    B, C, Hi, Wi, fine, coarse, c = _nearest_geom(kw)
+    acc = torch.zeros(B * Hi * Wi, C, dtype=torch.float64)
+    acc.index_add_(0, coarse, _rd(kw["a"], fine[:, None] * kw["ld_a"] + c))
+    _wr(kw["out"], (torch.arange(B * Hi * Wi)[:, None] * kw["ld_out"] + c).reshape(-1), acc.reshape(-1))
+
+
+def _bbox_kinds(kw, nch):
+    """Kind of every output channel: 0 identity, 1 s0 * x, 2 exp(s1 * x), 3 exp(s2 * x) + 1e-6, 4 relu(s3 * x)."""
+    kinds = []
+    for j in range(nch):
+        if kw.get("scales") is None:
+            kinds.append(0)
+        elif kw.get("bbox2d") and j >= nch - 4:
+            kinds.append(4)
+        else:
+            kinds.append(1 if j < 2 else 2 if j == 2 else 3 if j < 6 else 0)
+    return kinds
+
+
+def _bbox_geom(kw):
+    ng = int(kw["ngroups"])
+    dims = [int(v) for v in kw["dims"][:ng]]
+    ldx = [int(v) for v in kw["ldx"][:ng]]
+    B, H, W = (int(kw[k]) for k in ("B", "H", "W"))
+    pix = torch.arange(B * H * W)
+    xs = [_rd(kw["x"][g], pix[:, None] * ldx[g] + torch.arange(dims[g])[None, :]) for g in range(ng)]
+    nch = sum(dims)
+    hw = H * W
+    oidx = ((pix // hw)[:, None] * nch + torch.arange(nch)[None, :]) * hw + (pix % hw)[:, None]         # NCHW offset of (pixel, channel)
+    sc = _rd(kw["scales"], torch.arange(4)) if kw.get("scales") is not None else None
+    return ng, dims, ldx, pix, torch.cat(xs, 1), nch, oidx, sc, _bbox_kinds(kw, nch)
+
+
+def fcos_bbox_post(**kw):
+    ng, dims, ldx, pix, x, nch, oidx, sc, kinds = _bbox_geom(kw)
+    cols = []
+    for j, kd in enumerate(kinds):
+        xj = x[:, j]
+        cols.append(xj if kd == 0 else sc[0] * xj if kd == 1 else torch.exp(sc[1] * xj) if kd == 2 else
+                    torch.exp(sc[2] * xj) + float(torch.tensor(1e-6, dtype=torch.float32)) if kd == 3 else (sc[3] * xj).clamp_min(0.0))
+    _wr(kw["out"], oidx.reshape(-1), torch.stack(cols, 1).reshape(-1))
+
+
+def fcos_bbox_post_bwd(**kw):
+    ng, dims, ldx, pix, x, nch, oidx, sc, kinds = _bbox_geom(kw)
+    go = _rd(kw["dout"], oidx)
+    ds = torch.zeros(4, dtype=torch.float64)
+    cols = []
+    for j, kd in enumerate(kinds):
+        xj, gj = x[:, j], go[:, j]
+        if kd == 0:
+            cols.append(gj)
+        elif kd == 1:
+            cols.append(gj * sc[0]); ds[0] += (gj * xj).sum()
+        elif kd in (2, 3):
+            e = torch.exp(sc[kd - 1] * xj)
+            cols.append(gj * e * sc[kd - 1]); ds[kd - 1] += (gj * e * xj).sum()
+        else:
+            # the gate on the fp32 product, as the kernel takes it
+            on = (sc[3].float() * xj.float()) > 0
+            cols.append(torch.where(on, gj * sc[3], torch.zeros_like(gj))); ds[3] += torch.where(on, gj * xj, torch.zeros_like(gj)).sum()
+    gx = torch.stack(cols, 1)
+    j0 = 0
+    for g in range(ng):
+        if kw["dx"][g] is not None:
+            full = torch.zeros(pix.numel(), ldx[g], dtype=torch.float64)                                  # padding columns: zeros
+            full[:, :dims[g]] = gx[:, j0:j0 + dims[g]]
+            _wr(kw["dx"][g], (pix[:, None] * ldx[g] + torch.arange(ldx[g])[None, :]).reshape(-1), full.reshape(-1))
+        j0 += dims[g]
+    if sc is not None:
+        _wr(kw["dscales"], torch.arange(4), ds)
+
+
 _TABLE = dict(gather_rows=gather_rows, winattn_fwd=winattn_fwd, winattn_bwd=winattn_bwd, chanattn_fwd=chanattn_fwd, conv3s2_nchw=conv3s2_nchw, gemm=gemm, upconv4_expand=upconv4_expand, upconv4_gather=upconv4_gather, attn_fwd=attn_fwd, softmax_fwd=softmax_fwd, softmax_bwd=softmax_bwd,
               layernorm_fwd=layernorm_fwd, layernorm_bwd=layernorm_bwd, chan_logits=chan_logits, modulate=modulate,
               ctr_mix=ctr_mix, bilinear_fwd=bilinear_fwd, bilinear_bwd=bilinear_bwd, bn_stats=bn_stats,
@@ -1249,7 +1491,9 @@ _TABLE = dict(gather_rows=gather_rows, winattn_fwd=winattn_fwd, winattn_bwd=wina
               convt3x3s2_gather=convt3x3s2_gather, dwconv3x3s2_bwd=dwconv3x3s2_bwd, avgpool_ceil_bwd=avgpool_ceil_bwd,
               convt3x3s2_gather_bwd=convt3x3s2_gather_bwd, attn_bwd=attn_bwd, grad_sqnorm=grad_sqnorm, adam_step=adam_step, loss_label_stats=loss_label_stats,
               loss_fwd=loss_fwd, loss_bwd=loss_bwd, chanattn_bwd=chanattn_bwd, conv3s2_nchw_bwd=conv3s2_nchw_bwd, segcopy=segcopy,
-              ctr_weights=ctr_weights, ctr_weights_bwd=ctr_weights_bwd, detloss_fwd=detloss_fwd, detloss_bwd=detloss_bwd)
+              ctr_weights=ctr_weights, ctr_weights_bwd=ctr_weights_bwd, detloss_fwd=detloss_fwd, detloss_bwd=detloss_bwd,
+              groupnorm_fwd=groupnorm_fwd, groupnorm_bwd=groupnorm_bwd, dcn_im2col=dcn_im2col, dcn_col2im_bwd=dcn_col2im_bwd, nearest_add=nearest_add,
+              nearest_add_bwd=nearest_add_bwd, fcos_bbox_post=fcos_bbox_post, fcos_bbox_post_bwd=fcos_bbox_post_bwd)
 _POS = dict(boxes_overlap_bev=boxes_overlap_bev, nms_bev=nms_bev, patchify=patchify, resize_nchw=resize_nchw, patchify16=patchify16, cast2d=cast2d, split_cast=split_cast, pixshuf2=pixshuf2, colsum=colsum, colsum_batched=colsum_batched, add_rows=add_rows, rowscale_cast=rowscale_cast, rowscale_cast_colsum=rowscale_cast_colsum)
 
 

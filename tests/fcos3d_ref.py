@@ -22,8 +22,9 @@ def points(sizes, strides, device):
     return out
 
 
-def assign_single(e, pts, lvl_of, strides, rr, radius, alpha, num_classes):
-    """one image -> labels [P] int64, targets [P, 13] (offsets and ltrb / stride), centerness [P]"""
+def assign_single(e, pts, lvl_of, strides, rr, radius, alpha, num_classes, dists_out=None):
+    """one image -> labels [P] int64, targets [P, 13] (offsets and ltrb / stride), centerness [P]; dists_out (a list) receives the masked
+    point-to-gt distance matrix [P, n] the assignment takes its minimum over"""
     P = pts.shape[0]
     dev = pts.device
     n = e['label'].shape[0]
@@ -47,6 +48,8 @@ def assign_single(e, pts, lvl_of, strides, rr, radius, alpha, num_classes):
     dists = torch.sqrt(dx * dx + dy * dy)
     dists[~inside] = INF
     dists[~in_range] = INF
+    if dists_out is not None:
+        dists_out.append(dists.clone())
     md, mi = dists.min(dim=1)
     lab = e['label'].to(dev).long()[mi]
     lab[md == INF] = num_classes
@@ -59,7 +62,7 @@ def assign_single(e, pts, lvl_of, strides, rr, radius, alpha, num_classes):
     return lab, tgt, torch.exp(-alpha * rel)
 
 
-def assign(params, labels, sizes, device='cpu'):
+def assign(params, labels, sizes, device='cpu', dists_out=None):
     """-> keep (labelled batch indices), labels [n, P], targets [n, P, 13], centerness [n, P] (points in level order)"""
     strides = params['strides']
     pts = torch.cat(points(sizes, strides, device))
@@ -67,7 +70,7 @@ def assign(params, labels, sizes, device='cpu'):
     dl, num = labels['det_labels'], labels['det_label_number']
     keep = [i for i in range(len(dl)) if int(num[i]) != 0]
     res = [assign_single(dl[i], pts, lvl_of, strides, params['regress_ranges'], params.get('center_sample_radius', 1.5),
-                         params.get('centerness_alpha', 2.5), params['num_classes']) for i in keep]
+                         params.get('centerness_alpha', 2.5), params['num_classes'], dists_out) for i in keep]
     if not res:
         return keep, None, None, None
     return keep, torch.stack([r[0] for r in res]), torch.stack([r[1] for r in res]), torch.stack([r[2] for r in res])

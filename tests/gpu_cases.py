@@ -1,7 +1,8 @@
 """GPU parity cases: the C-ABI entry points of libmtt_hip.so against the CPU emulator (oracle/abi_emul.py) on identical seeded
 buffers; the entry points no case runs are listed in COVERED_ELSEWHERE with the device test that checks them.  `compare` judges EVERY
 buffer's whole storage: the norm-wise error, a bound per written element, and bitwise-unchanged memory outside the emulator's written
-set (output buffers are filled with non-zero sentinels), so stray writes show up as well as wrong values.  Used by tests/test_gpu_ops.py
+set (output buffers are filled with non-zero sentinels, integer ones included; the det cases put 1e30 in the pitch padding of inputs), so stray
+writes and stray reads show up as well as wrong values.  Tensor arguments may also sit in pointer arrays (list-valued fields).  Used by tests/test_gpu_ops.py
 (pytest, `-m gpu`), tools/gpu_diag.py (runs all cases without stopping and writes a JSON report) and, on the host,
 tests/test_parity_comparator.py (the comparator against planted defects).
 """
@@ -47,7 +48,12 @@ def _arg_tensors(kw):
     out = []
     for lk in ("args", "xargs"):
         out += [(f"{lk}[{i}]", a) for i, a in enumerate(kw.get(lk) or ()) if isinstance(a, torch.Tensor)]
-    return out + [(k, v) for k, v in kw.items() if isinstance(v, torch.Tensor)]
+    for k, v in kw.items():
+        if isinstance(v, torch.Tensor):
+            out.append((k, v))
+        elif k not in ("args", "xargs") and isinstance(v, (list, tuple)):          # a pointer array (the bbox tail's x[g] / dx[g])
+            out += [(f"{k}[{i}]", a) for i, a in enumerate(v) if isinstance(a, torch.Tensor)]
+    return out
 
 
 def _split_pairs(kw, tol):
@@ -80,6 +86,8 @@ def clone_storages(kw):
     for k, v in kw.items():
         if isinstance(v, torch.Tensor):
             out[k] = cp(v)
+        elif k not in ("args", "xargs") and isinstance(v, (list, tuple)):
+            out[k] = [cp(a) if isinstance(a, torch.Tensor) else a for a in v]
     return out, store
 
 
@@ -193,11 +201,30 @@ def compare(kw, tol, pre, emu, written, dev, skip=()):
     return dict(ok=ok, errs=errs)
 
 
+# entry points whose workspace has a size query in the library: entry -> the query's name (mtt_<query>_ws_floats(desc))
+WS_QUERY = {"groupnorm_fwd": "groupnorm", "groupnorm_bwd": "groupnorm", "dcn_col2im_bwd": "dcn_col2im", "fcos_bbox_post_bwd": "fcos_bbox_post"}
+
+
+def _device_ws(name, kw, gpu_kw):
+    """The workspace of the entry points that have a library query, sized by that query at run time (the cases carry none: the emulator
+    ignores it) and filled with 0xFF bytes (NaN as floats, all-ones mask words), so a read of a part the kernel did not write shows."""
+    lib = pkg()._lib
+    if name in WS_QUERY:
+        n = lib.ws_floats(WS_QUERY[name], **{k: v for k, v in kw.items() if isinstance(v, int) and not isinstance(v, bool)})
+        assert n > 0, f"mtt_{WS_QUERY[name]}_ws_floats rejects the case's geometry"
+        gpu_kw["ws"] = torch.full((4 * n,), 0xFF, dtype=torch.uint8, device="cuda")
+    elif name == "nms_bev":
+        n = pkg().iou3d.nms_ws_bytes(kw["args"][1])
+        assert n > 0
+        gpu_kw["args"][6] = torch.full((n,), 0xFF, dtype=torch.uint8, device="cuda")
+
+
 def run_case(name, kw, outputs, tol):
     """Run entry `name` with CPU emulator and on the GPU on identical copies of every storage, then `compare` them.
     Returns dict(ok, errs)."""
     lib = pkg()._lib
     tensors = {k: v for k, v in kw.items() if isinstance(v, torch.Tensor)}
+    lists = {k: v for k, v in kw.items() if k not in ("args", "xargs") and isinstance(v, (list, tuple))}
     # GPU copies sharing storage structure
     gpu_store, gpu_kw, pre = {}, dict(kw), {}
 
@@ -218,6 +245,9 @@ def run_case(name, kw, outputs, tol):
             gpu_kw[lk] = [to_gpu(a) if isinstance(a, torch.Tensor) else a for a in kw[lk]]
     for k, t in tensors.items():
         gpu_kw[k] = to_gpu(t)
+    for k, v in lists.items():
+        gpu_kw[k] = [to_gpu(a) if isinstance(a, torch.Tensor) else a for a in v]
+    _device_ws(name, kw, gpu_kw)
     lib.call(name, **gpu_kw)
     torch.cuda.synchronize()
     with abi_emul.tracking() as written:
@@ -1157,21 +1187,210 @@ def loss_cases():
     return cases
 
 
+GAP = 1e30          # pitch padding of an INPUT the kernel must never read: a stray read shows as a value error (outputs hold sentinels)
+
+
+def _padded(vals, ld, gap, dtype=torch.float32):
+    """[rows, ld] buffer holding vals [rows, C] in its first C columns and `gap` in the others."""
+    t = torch.full((vals.shape[0], ld), gap, dtype=dtype)
+    t[:, :vals.shape[1]] = vals.to(dtype)
+    return t
+
+
+def det_cases():
+    """The FCOS3D head and FPN neck kernels of csrc/det_ops.hip (ABI 14) at the smallest shapes that reach each path: GroupNorm's second
+    lane trip of the per-group merge (80 entries), a one-row tail chunk, HW = 1, a channel loop past 256 threads, pitch padding; the
+    deformable im2col / col2im at C > 64 and C % 8 != 0, stride 2, pad = dil = 2, 1 x 1 and one-column maps, offsets that are absent, zero,
+    integral, random, all outside, all in one cell and exactly on the -1 / H borders, every mask form, the production layout (offset and
+    mask as views of one 32-column buffer); the nearest add up, down and at ratio 1, in place; the bbox tail over one and four workgroups.
+    Workspaces are sized by the library's queries in run_case; the cases carry none."""
+    cases = []
+    g = torch.Generator().manual_seed(53)
+    # split outputs: hi + lo carries 16 significant bits (2^-17 |v| of representation error, 4e-5 of s at a 5-sigma element), so the pair's sum
+    # is judged at the bound of the split GEMM outputs (TOL_SPLIT_D: 2e-5 norm-wise, 2e-4 s per element), the hi plane as a bf16 storage
+    SPL = lambda h, l: dict(TOL_ROW, split=2e-5, split_pairs=[(h, l)])
+
+    # ---- GroupNorm (+ReLU): (tag, Z, B, HW, C, G, ld, relu, x / y / dy / dx dtypes, dgamma + dbeta, mean of x)
+    gn = (("cpg1_2chunks", 2, 2, 35, 32, 32, 32, 1, F32, F32, F32, F32, True, 0.0),
+          ("tail_row_mean100", 1, 3, 33, 64, 8, 64, 0, F32, F32, F32, F32, True, 100.0),
+          ("80entries", 2, 2, 289, 64, 8, 64, 1, F32, SPLIT, F32, F32, True, 0.0),
+          ("80entries_bf16", 2, 2, 289, 64, 8, 64, 1, BF16, BF16, BF16, BF16, False, 0.0),
+          ("hw1_cpg1", 1, 2, 1, 32, 32, 32, 1, F32, F32, F32, F32, True, 0.0),
+          ("hw1_cpg8", 1, 2, 1, 64, 8, 64, 0, F32, F32, F32, F32, True, 0.0),
+          ("c288_ld320", 1, 1, 40, 288, 32, 320, 1, F32, F32, F32, F32, True, 0.0),
+          ("c48_ld56", 1, 2, 64, 48, 4, 56, 0, BF16, F32, F32, BF16, False, 0.0),
+          ("c48_ld56_relu_split", 1, 2, 64, 48, 4, 56, 1, F32, SPLIT, BF16, F32, True, 0.0))
+    for tag, Z, B, HW, C, G, ld, relu, xdt, ydt, dydt, dxdt, params, shift in gn:
+        rows, N = Z * B * HW, Z * B
+        x = _padded(rnd(g, rows, C) + shift, ld, GAP, DT[xdt])
+        base = dict(x=x, gamma=1.0 + 0.3 * rnd(g, Z * C), beta=0.3 * rnd(g, Z * C), Z=Z, B=B, HW=HW, C=C, G=G, ld=ld, x_dtype=xdt, relu=relu, eps=1e-5)
+        ydtype = torch.float32 if ydt == F32 else torch.bfloat16
+        kw = dict(base, y=torch.full((rows, ld), 7.0, dtype=ydtype), y_lo=torch.full((rows, ld), 5.0, dtype=torch.bfloat16) if ydt == SPLIT else None,
+                  y_dtype=ydt, mean=torch.full((N * G,), 9.0), rstd=torch.full((N * G,), 9.0))
+        cases.append((f"groupnorm_fwd_{tag}", "groupnorm_fwd", kw, SPL("y", "y_lo") if ydt == SPLIT else TOL_ROW))
+        # the backward reads the statistics the forward stored: the emulator's, rounded to fp32
+        mean, rstd = torch.zeros(N * G), torch.zeros(N * G)
+        abi_emul.call("groupnorm_fwd", **dict(base, y=torch.zeros(rows, ld), y_dtype=F32, mean=mean, rstd=rstd))
+        kw = dict(base, mean=mean, rstd=rstd, dy=_padded(rnd(g, rows, C), ld, GAP, DT[dydt]), dy_dtype=dydt, dx=torch.full((rows, ld), 7.0, dtype=DT[dxdt]),
+                  dx_dtype=dxdt, dgamma=torch.full((Z * C,), 9.0) if params else None, dbeta=torch.full((Z * C,), 9.0) if params else None)
+        cases.append((f"groupnorm_bwd_{tag}", "groupnorm_bwd", kw, TOL_ROW))
+
+    # ---- modulated deformable im2col / col2im
+    def dcn(tag, B, H, W, C, stride, off, mask, pad=1, dil=1, xdt=F32, odt=F32, cdt=F32, gdt=F32, dxdt=F32, ldx_extra=0, ldc_extra=0, ld_off=18,
+            layout32=False, want_dx=True, want_doff=True):
+        Cp = (C + 7) // 8 * 8
+        Ho, Wo = (H + 2 * pad - 2 * dil - 1) // stride + 1, (W + 2 * pad - 2 * dil - 1) // stride + 1
+        rows, ldx, ldc = B * Ho * Wo, Cp + ldx_extra, 9 * Cp + ldc_extra
+        xv = torch.zeros(B * H * W, Cp)
+        xv[:, :C] = rnd(g, B * H * W, C)
+        r, k = torch.arange(rows)[:, None], torch.arange(9)[None, :]
+        bh = (((r % (Ho * Wo)) // Wo) * stride - pad + (k // 3) * dil).float()                  # the taps' positions without offsets
+        bw = (((r % (Ho * Wo)) % Wo) * stride - pad + (k % 3) * dil).float()
+        ov = None
+        if off == "zero":
+            ov = torch.zeros(rows, 18)
+        elif off == "int":
+            ov = torch.randint(-3, 4, (rows, 18), generator=g).float()
+        elif off == "randn3":
+            ov = 3.0 * rnd(g, rows, 18)
+        elif off == "far":
+            ov = 50.0 + 5.0 * torch.rand(rows, 18, generator=g)
+        elif off in ("onecell", "border"):
+            if off == "onecell":                                                                  # every sample inside the floor cell (H // 2, W // 2 - 1)
+                th = H // 2 + 0.1 + 0.8 * torch.rand(rows, 9, generator=g)
+                tw = W // 2 - 1 + 0.1 + 0.8 * torch.rand(rows, 9, generator=g)
+            else:                                                                                 # exactly on -1, -0.5, H - 1, H - 0.5, H (likewise w), every pairing
+                sidx = r * 9 + k
+                th = torch.tensor([-1.0, -0.5, H - 1.0, H - 0.5, float(H)])[sidx % 5]
+                tw = torch.tensor([-1.0, -0.5, W - 1.0, W - 0.5, float(W)])[(sidx // 5) % 5]
+            ov = torch.stack([th - bh, tw - bw], 2).reshape(rows, 18)
+            if off == "border":
+                assert torch.equal((bh + ov[:, 0::2]), th) and torch.equal((bw + ov[:, 1::2]), tw)   # the fp32 sum lands exactly on the border
+        mv = None if mask is None else torch.full((rows, 9), -80.0) if mask == "m80" else rnd(g, rows, 9)
+        kw = dict(x=_padded(xv, ldx, GAP, DT[xdt]), x_dtype=xdt, ldx=ldx, mask_sigmoid=0 if mask == "raw" else 1, off_dtype=odt, B=B, H=H, W=W, C=C, Cp=Cp,
+                  Ho=Ho, Wo=Wo, stride=stride, pad=pad, dil=dil, ldc=ldc)
+        dkw = {}
+        if layout32:                                 # the head's layout: the offset conv's 27 outputs in one 32-column buffer, their gradients in another
+            om = torch.full((rows, 32), GAP, dtype=DT[odt])
+            om[:, :18], om[:, 18:27] = ov.to(DT[odt]), mv.to(DT[odt])
+            dom = torch.full((rows, 32), 7.0, dtype=DT[odt])
+            kw.update(offset=om[:, :18], ld_off=32, mask=om[:, 18:27], ld_mask=32)
+            dkw.update(doffset=dom[:, :18], dmask=dom[:, 18:27])
+        else:
+            if ov is not None:
+                kw.update(offset=_padded(ov, ld_off, GAP, DT[odt]), ld_off=ld_off)
+                if want_doff:
+                    dkw.update(doffset=torch.full((rows, ld_off), 7.0, dtype=DT[odt]))
+            if mv is not None:
+                kw.update(mask=mv.to(DT[odt]), ld_mask=9)
+                if want_doff:
+                    dkw.update(dmask=torch.full((rows, 9), 7.0, dtype=DT[odt]))
+        cdtype = torch.float32 if cdt == F32 else torch.bfloat16
+        fkw = dict(kw, col=torch.full((rows, ldc), 7.0, dtype=cdtype), col_lo=torch.full((rows, ldc), 5.0, dtype=torch.bfloat16) if cdt == SPLIT else None, col_dtype=cdt)
+        cases.append((f"dcn_im2col_{tag}", "dcn_im2col", fkw, SPL("col", "col_lo") if cdt == SPLIT else TOL_ROW))
+        bkw = dict(kw, dcol=_padded(rnd(g, rows, 9 * Cp), ldc, GAP, DT[gdt]), dcol_dtype=gdt, dx_dtype=dxdt,
+                   dx=torch.full((B * H * W, ldx), 7.0, dtype=DT[dxdt]) if want_dx else None, **dkw)
+        cases.append((f"dcn_col2im_bwd_{tag}", "dcn_col2im_bwd", bkw, TOL_ROW))
+
+    dcn("s1_randn_sigmoid", 2, 9, 11, 24, 1, "randn3", "sigmoid")
+    dcn("s2_plain_bf16", 2, 9, 11, 24, 2, None, None, xdt=BF16, cdt=BF16, gdt=BF16, dxdt=BF16)
+    dcn("c100_bf16off_raw_split_pitches", 3, 5, 7, 100, 1, "randn3", "raw", odt=BF16, cdt=SPLIT, ldx_extra=8, ldc_extra=8)
+    dcn("1x1_zero_m80", 1, 1, 1, 8, 1, "zero", "m80")
+    dcn("6x1_int_dxonly", 1, 6, 1, 16, 1, "int", None, want_doff=False)
+    dcn("pad2dil2_border", 1, 7, 7, 72, 1, "border", "sigmoid", pad=2, dil=2)
+    dcn("s1_far", 2, 9, 11, 24, 1, "far", "sigmoid")
+    dcn("s1_onecell_raw", 2, 9, 11, 24, 1, "onecell", "raw")
+    dcn("s2_layout32", 2, 9, 11, 24, 2, "randn3", "sigmoid", layout32=True)
+    dcn("c100_nodx_ldoff24", 3, 5, 7, 100, 1, "randn3", "sigmoid", ld_off=24, want_dx=False)
+    dcn("s1_int_raw", 2, 9, 11, 24, 1, "int", "raw")
+
+    # ---- FPN nearest add: (Hi, Wi) -> (Ho, Wo); up, ragged up, ratio 1 (in place), from one pixel, down (coarse pixels without a reader)
+    for (Hi, Wi), (Ho, Wo), C, ld, dt, alias in (((6, 10), (12, 20), 16, 24, F32, False), ((5, 7), (12, 17), 5, 8, BF16, False),
+                                                 ((6, 10), (6, 10), 16, 24, F32, True), ((1, 1), (9, 13), 16, 24, BF16, False),
+                                                 ((12, 20), (5, 7), 16, 24, F32, False), ((12, 20), (5, 7), 16, 16, BF16, False)):
+        B = 2
+        tag = f"{Hi}x{Wi}_to_{Ho}x{Wo}_c{C}_ld{ld}_{'bf16' if dt else 'f32'}"
+        geom = dict(B=B, C=C, Ho=Ho, Wo=Wo, Hi=Hi, Wi=Wi, ld_a=ld, ld_src=ld, ld_out=ld, dtype=dt)
+        a = _padded(rnd(g, B * Ho * Wo, C), ld, 7.0 if alias else GAP, DT[dt])                  # in place: a's padding is the output's (a sentinel)
+        out = a if alias else torch.full((B * Ho * Wo, ld), 7.0, dtype=DT[dt])
+        cases.append((f"nearest_add_{tag}{'_inplace' if alias else ''}", "nearest_add",
+                      dict(geom, a=a, src=_padded(rnd(g, B * Hi * Wi, C), ld, GAP, DT[dt]), out=out), TOL_ROW))
+        cases.append((f"nearest_add_bwd_{tag}", "nearest_add_bwd",
+                      dict(geom, a=_padded(rnd(g, B * Ho * Wo, C), ld, GAP, DT[dt]), src=None, out=torch.full((B * Hi * Wi, ld), 7.0, dtype=DT[dt])), TOL_ROW))
+
+    # ---- FCOS3D bbox tail: one workgroup (70 pixels) and four with a ragged last one (819 pixels: the partials -> final sum path)
+    for tag, B, H, W, dims, bbox2d, scales, pitch, skip_dx in (("1wg", 2, 5, 7, (2, 1, 3, 3, 4), 1, True, 0, None), ("4wg_ld8", 3, 13, 21, (2, 1, 3, 3, 4), 1, True, 8, 3),
+                                                               ("nobbox2d_ld8", 2, 5, 7, (2, 1, 3, 3), 0, True, 8, None), ("copy6_4wg", 3, 13, 21, (6,), 0, False, 0, None),
+                                                               ("copy1_ld8", 2, 5, 7, (1,), 0, False, 8, None)):
+        npix, nch, ng = B * H * W, sum(dims), len(dims)
+        ldx = [pitch or d for d in dims]
+        xs = [0.5 * rnd(g, npix, d) for d in dims]
+        sc = torch.tensor([0.9, 1.1, 0.7, 1.3]) if scales else None
+        if bbox2d:                                                                                # the ReLU gate of the backward: keep scales[3] * x off zero
+            xs[-1] = torch.where(xs[-1].abs() < 2e-3, torch.full_like(xs[-1], 0.01), xs[-1])
+            assert float((sc[3] * xs[-1]).abs().min()) >= 1e-3
+        base = dict(x=[_padded(x, l, GAP) for x, l in zip(xs, ldx)], ldx=ldx, dims=list(dims), ngroups=ng, scales=sc, bbox2d=bbox2d, B=B, H=H, W=W)
+        cases.append((f"fcos_bbox_post_{tag}", "fcos_bbox_post", dict(base, out=torch.full((B, nch, H, W), 7.0)), TOL_ROW))
+        cases.append((f"fcos_bbox_post_bwd_{tag}", "fcos_bbox_post_bwd",
+                      dict(base, dout=rnd(g, B, nch, H, W), dx=[None if i == skip_dx else torch.full((npix, l), 7.0) for i, l in enumerate(ldx)],
+                           dscales=torch.full((4,), 9.0) if scales else None), TOL_ROW))
+    return cases
+
+
+NMS_MARGIN = 1e-4     # no pair's oracle IoU within this of a case's threshold: 5 x the 2e-5 device-vs-glibc bound of test_hip_pairwise_matches_reference_golden
+
+NMS_THRESHOLDS = (0.3, 0.5)
+_IOU_UPPER = {}
+
+
+def _iou_upper(n, rotated):
+    """(boxes, the oracle's IoU of every pair i < j) of the n NMS boxes, cached (shared by the thresholds).  Seed n; where a pair lies
+    within NMS_MARGIN of a threshold the next of n + 1000, n + 2000, ... without one (n = 65 axis-aligned: seed 65 has IoU(12, 38) =
+    0.29991, 9.0e-5 under 0.3, and box 12 is kept)."""
+    import numpy as np
+    from oracle import iou3d_oracle as io
+    from tests.golden.make_iou3d_golden import boxes
+    if (n, rotated) not in _IOU_UPPER:
+        fn = io.iou_bev if rotated else io.iou_normal
+        for seed in range(n, n + 10000, 1000):
+            bx = boxes(np.random.default_rng(seed), n, 0.9 * max(n, 4) ** 0.5)
+            ious = np.array([float(fn(bx[i], bx[j])) for i in range(n) for j in range(i + 1, n)])
+            if all(not (np.abs(ious - thr) < NMS_MARGIN).any() for thr in NMS_THRESHOLDS):
+                break
+        _IOU_UPPER[(n, rotated)] = (bx, ious)
+    return _IOU_UPPER[(n, rotated)]
+
+
+def iou3d_cases():
+    """Rotated-box overlap / IoU and both NMS variants (csrc/iou3d.hip) against oracle/iou3d_oracle.py.  Pairwise: the degenerate
+    configurations of make_iou3d_golden.special() and random boxes, one partial wave, whole waves, a 65-wide row.  NMS: n = 1, 63, 64, 65, 129
+    (one box, a ragged / full / just-over tile, three column blocks), keep pre-filled with -7 so that keep[num_out:] must stay untouched.
+    The device's sinf / cosf / atan2f differ from glibc's by ulps, so a pair whose IoU sat on the threshold could flip: the builder
+    asserts that no pair is within NMS_MARGIN of it."""
+    import numpy as np
+    from tests.golden.make_iou3d_golden import boxes, special
+    cases = []
+    pool = np.concatenate([special(), boxes(np.random.default_rng(17), 80, 4.0)])
+    for na, nb in ((7, 5), (33, 64), (9, 65)):
+        a, b = torch.from_numpy(pool[:na].copy()), torch.from_numpy(pool[3:3 + nb].copy())
+        for iou in (0, 1):
+            cases.append((f"boxes_{'iou' if iou else 'overlap'}_bev_{na}x{nb}", "boxes_overlap_bev", dict(args=[a, na, b, nb, torch.full((na * nb,), 7.0), iou]), TOL_ROW))
+    for n in (1, 63, 64, 65, 129):
+        for rotated in (1, 0):
+            bx, ious = _iou_upper(n, rotated)
+            for thr in NMS_THRESHOLDS:
+                assert not (np.abs(ious - thr) < NMS_MARGIN).any(), (n, rotated, thr)
+                cases.append((f"nms_bev_n{n}_{'rot' if rotated else 'axis'}_t{thr}", "nms_bev",
+                              dict(args=[torch.from_numpy(bx.copy()), n, thr, rotated, torch.full((n,), -7, dtype=torch.int64),
+                                         torch.full((1,), -7, dtype=torch.int32), None]), TOL_ROW))
+    return cases
+
+
 # entry points the parity cases above do not run, and the test that checks each of them on the device instead
 COVERED_ELSEWHERE = {
     "adam_step": "tests/test_gpu_train.py::test_fused_clip_adam_matches_torch_on_gpu",
     "grad_sqnorm": "tests/test_gpu_train.py::test_fused_clip_adam_matches_torch_on_gpu",
     "segcopy": "tests/test_gpu_ops.py::test_segcopy_packs_refresh_and_gradient_scatter_on_device",
-    "boxes_overlap_bev": "tests/test_iou3d.py::test_hip_pairwise_matches_reference_golden",
-    "nms_bev": "tests/test_iou3d.py::test_hip_nms_matches_reference_golden",
-    "groupnorm_fwd": "tests/test_gpu_det_head.py::test_groupnorm_relu_fwd_bwd",
-    "groupnorm_bwd": "tests/test_gpu_det_head.py::test_groupnorm_relu_fwd_bwd",
-    "dcn_im2col": "tests/test_gpu_det_head.py::test_dcn_layer_fwd_bwd",
-    "dcn_col2im_bwd": "tests/test_gpu_det_head.py::test_dcn_layer_fwd_bwd",
-    "nearest_add": "tests/test_gpu_det_head.py::test_nearest_add_fwd_bwd",
-    "nearest_add_bwd": "tests/test_gpu_det_head.py::test_nearest_add_fwd_bwd",
-    "fcos_bbox_post": "tests/test_gpu_det_head.py::test_bbox_tail_fwd_bwd",
-    "fcos_bbox_post_bwd": "tests/test_gpu_det_head.py::test_bbox_tail_fwd_bwd",
     "fcos3d_targets": "tests/test_gpu_fcos3d.py::test_targets_match_the_reference_fixture",
     "fcos3d_loss_fwd": "tests/test_gpu_fcos3d.py::test_losses_and_gradients_match_the_reference_fixture",
     "fcos3d_loss_bwd": "tests/test_gpu_fcos3d.py::test_losses_and_gradients_match_the_reference_fixture",
@@ -1179,4 +1398,4 @@ COVERED_ELSEWHERE = {
 
 
 def all_cases():
-    return gemm_cases() + attn_cases() + row_cases() + invpt_cases() + upconv_cases() + swin_cases() + loss_cases()
+    return gemm_cases() + attn_cases() + row_cases() + invpt_cases() + upconv_cases() + swin_cases() + loss_cases() + det_cases() + iou3d_cases()

@@ -272,3 +272,168 @@ def test_segcopy_and_ctr_mix_bf16_output():
     E.call("ctr_mix", fea=fea, out=out, wmix=wm, T=T, B=B, rows_per_b=rpb, ld=ld, C=C, fea_dtype=E_F32, accumulate=0, out_dtype=1)
     ref = torch.einsum("bts,sbrc->tbrc", wm, fea.view(T, B, rpb, ld)).reshape(T, B * rpb, ld)
     assert torch.allclose(out.float(), ref, atol=2e-2, rtol=1e-2)
+
+
+# ---- ABI 14 (the FCOS3D head and FPN neck): the fp64 restatements against independent torch expressions, autograd for the backwards.
+# Inputs are fp32-representable values held in fp64 tensors (so the emulator's fp32 decisions see the reference's values) and stay at
+# least 1e-3 away from every gate / integer, asserted below; agreement is to fp64 rounding.
+def _close(a, b, rel=1e-10):
+    return float((a.double() - b.double()).abs().max()) <= rel * max(float(b.double().abs().max()), 1e-30)
+
+
+def _nhwc(x, ld=None, fill=0.0):
+    """[B, C, H, W] -> rows [B*H*W, ld] (fp64), padding columns = fill."""
+    B, Cn = x.shape[:2]
+    r = x.reshape(B, Cn, -1).permute(0, 2, 1).reshape(-1, Cn)
+    out = torch.full((r.shape[0], ld or Cn), fill, dtype=torch.float64)
+    out[:, :Cn] = r
+    return out
+
+
+def test_groupnorm_fwd_bwd_vs_torch_group_norm():
+    eps = float(torch.tensor(1e-5, dtype=torch.float32))
+    for seed, (Z, B, HW, C, G, ld, relu, bf16) in enumerate(((2, 2, 6, 12, 4, 16, 1, False), (1, 3, 5, 8, 8, 8, 0, False), (1, 2, 1, 8, 2, 8, 1, False),
+                                                           (2, 1, 7, 6, 1, 8, 1, True))):
+        g = g_(40 + seed)
+        rf = lambda *s: torch.randn(*s, generator=g).to(torch.bfloat16 if bf16 else torch.float32).double()
+        x = (rf(Z, B, C, HW) + 3.0).requires_grad_(True)
+        gamma, beta = (1.0 + 0.3 * rf(Z, C)).requires_grad_(True), (0.3 * rf(Z, C)).requires_grad_(True)
+        dy = rf(Z, B, C, HW)
+        pre = torch.stack([F.group_norm(x[z], G, gamma[z], beta[z], eps) for z in range(Z)])
+        if relu:
+            assert float(pre.detach().abs().min()) >= 1e-3, seed
+        ref = F.relu(pre) if relu else pre
+        ref.backward(dy)
+        N = Z * B
+        xr = _nhwc(x.detach().reshape(N, C, HW), ld, 1e30)
+        y, mean, rstd = torch.full((N * HW, ld), 7.0, dtype=torch.float64), torch.zeros(N * G, dtype=torch.float64), torch.zeros(N * G, dtype=torch.float64)
+        geom = dict(x=xr, gamma=gamma.detach().reshape(-1), beta=beta.detach().reshape(-1), Z=Z, B=B, HW=HW, C=C, G=G, ld=ld, relu=relu, eps=1e-5)
+        E.call("groupnorm_fwd", **geom, y=y, mean=mean, rstd=rstd)
+        assert _close(y[:, :C], _nhwc(ref.detach().reshape(N, C, HW))) and float(y[:, C:].abs().max() if ld > C else 0.0) == 0.0
+        xg = x.detach().reshape(N, G, C // G, HW)
+        assert _close(mean.view(N, G), xg.mean((2, 3))) and _close(rstd.view(N, G), (xg.var((2, 3), unbiased=False) + eps).rsqrt())
+        dx, dg, db = torch.full((N * HW, ld), 7.0, dtype=torch.float64), torch.full((Z * C,), 9.0, dtype=torch.float64), torch.full((Z * C,), 9.0, dtype=torch.float64)
+        E.call("groupnorm_bwd", **geom, mean=mean, rstd=rstd, dy=_nhwc(dy.reshape(N, C, HW), ld, 1e30), dx=dx, dgamma=dg, dbeta=db)
+        assert _close(dx[:, :C], _nhwc(x.grad.reshape(N, C, HW))) and float(dx[:, C:].abs().max() if ld > C else 0.0) == 0.0
+        assert _close(dg, gamma.grad.reshape(-1)) and _close(db, beta.grad.reshape(-1))
+        dx2 = torch.full((N * HW, ld), 7.0, dtype=torch.float64)                                     # without the parameter gradients
+        E.call("groupnorm_bwd", **geom, mean=mean, rstd=rstd, dy=_nhwc(dy.reshape(N, C, HW), ld, 1e30), dx=dx2, dgamma=None, dbeta=None)
+        assert torch.equal(dx2, dx)
+
+
+def test_dcn_im2col_col2im_vs_restatement():
+    import det_ref
+    for seed, (B, H, W, C, stride, pad, dil, sig, has_off, has_mask) in enumerate(((2, 5, 6, 5, 1, 1, 1, 1, True, True), (1, 6, 7, 8, 2, 1, 1, 0, True, True),
+                                                                                 (2, 5, 5, 3, 1, 2, 2, 1, True, False), (1, 4, 5, 4, 2, 1, 1, 1, False, False))):
+        g = g_(60 + seed)
+        Cp = (C + 7) // 8 * 8
+        Ho, Wo = (H + 2 * pad - 2 * dil - 1) // stride + 1, (W + 2 * pad - 2 * dil - 1) // stride + 1
+        rows = B * Ho * Wo
+        x = torch.randn(B, C, H, W, generator=g).double().requires_grad_(True)
+        off = mlog = None
+        if has_off:
+            # multiples of 1/256 that are not integers: the fp32 sum with the integer tap position is exact and >= 3.9e-3 from an integer
+            q = torch.round(2.0 * torch.randn(B, 18, Ho, Wo, generator=g) * 256)
+            q = torch.where(q % 256 == 0, q + 1, q)
+            off = (q / 256).double().requires_grad_(True)
+            frac = off.detach() - torch.floor(off.detach())
+            assert float(torch.minimum(frac, 1 - frac).min()) >= 1e-3
+        if has_mask:
+            mlog = torch.randn(B, 9, Ho, Wo, generator=g).double().requires_grad_(True)
+        wsel = torch.zeros(9 * C, C, 3, 3, dtype=torch.float64)                                     # output channel k*C + c = column (tap k, channel c)
+        for k in range(9):
+            wsel[k * C + torch.arange(C), torch.arange(C), k // 3, k % 3] = 1.0
+        mask = None if mlog is None else torch.sigmoid(mlog) if sig else mlog
+        ref = det_ref.dcn_v2(x, off, mask, wsel, None, stride=stride, pad=pad, dil=dil)          # [B, 9*C, Ho, Wo]
+        dcol = torch.randn(ref.shape, generator=g).double()
+        ref.backward(dcol)
+        ldx, ldc = Cp + 8, 9 * Cp + 8
+        xr = _nhwc(x.detach(), Cp)
+        xr = torch.cat([xr, torch.full((xr.shape[0], 8), 1e30, dtype=torch.float64)], 1)
+        kw = dict(x=xr, ldx=ldx, mask_sigmoid=sig, B=B, H=H, W=W, C=C, Cp=Cp, Ho=Ho, Wo=Wo, stride=stride, pad=pad, dil=dil, ldc=ldc)
+        if has_off:
+            kw.update(offset=_nhwc(off.detach(), 24, 1e30), ld_off=24)
+        if has_mask:
+            kw.update(mask=_nhwc(mlog.detach()), ld_mask=9)
+        col = torch.full((rows, ldc), 7.0, dtype=torch.float64)
+        E.call("dcn_im2col", **kw, col=col)
+        want = torch.zeros(rows, 9, Cp, dtype=torch.float64)
+        want[:, :, :C] = _nhwc(ref.detach()).view(rows, 9, C)
+        assert _close(col[:, :9 * Cp].reshape(rows, 9, Cp), want) and float((col[:, 9 * Cp:] - 7.0).abs().max()) == 0.0
+        dc = torch.full((rows, ldc), 1e30, dtype=torch.float64)
+        dcv = torch.randn(rows, 9, Cp, generator=g).double()                                      # the padding channels hold anything
+        dcv[:, :, :C] = _nhwc(dcol).view(rows, 9, C)
+        dc[:, :9 * Cp] = dcv.reshape(rows, 9 * Cp)
+        dx = torch.full((B * H * W, ldx), 7.0, dtype=torch.float64)
+        dof = torch.full((rows, 24), 7.0, dtype=torch.float64) if has_off else None
+        dm = torch.full((rows, 9), 7.0, dtype=torch.float64) if has_mask else None
+        E.call("dcn_col2im_bwd", **kw, dcol=dc, dx=dx, doffset=dof, dmask=dm)
+        assert _close(dx[:, :C], _nhwc(x.grad)) and float(dx[:, C:Cp].abs().max() if Cp > C else 0.0) == 0.0 and float((dx[:, Cp:] - 7.0).abs().max()) == 0.0
+        if has_off:
+            assert _close(dof[:, :18], _nhwc(off.grad)) and float((dof[:, 18:] - 7.0).abs().max()) == 0.0
+        if has_mask:
+            assert _close(dm, _nhwc(mlog.grad))
+        if has_off:                                                                              # dx = NULL with doffset set
+            dof2 = torch.full((rows, 24), 7.0, dtype=torch.float64)
+            E.call("dcn_col2im_bwd", **kw, dcol=dc, dx=None, doffset=dof2, dmask=None)
+            assert torch.equal(dof2, dof)
+
+
+def test_nearest_add_fwd_bwd_vs_interpolate():
+    for seed, ((Hi, Wi), (Ho, Wo), C, ld, bf16) in enumerate((((5, 7), (12, 17), 5, 8, False), ((12, 20), (5, 7), 4, 4, False), ((6, 10), (6, 10), 3, 8, False),
+                                                            ((1, 1), (9, 13), 2, 8, True), ((6, 10), (12, 20), 4, 8, True))):
+        g = g_(80 + seed)
+        B = 2
+        rf = lambda *s: torch.randn(*s, generator=g).to(torch.bfloat16 if bf16 else torch.float32).double()
+        a, src = rf(B, C, Ho, Wo), rf(B, C, Hi, Wi).requires_grad_(True)
+        ref = a + F.interpolate(src, size=(Ho, Wo), mode="nearest")
+        dy = rf(B, C, Ho, Wo)
+        ref.backward(dy)
+        geom = dict(B=B, C=C, Ho=Ho, Wo=Wo, Hi=Hi, Wi=Wi, ld_a=ld, ld_src=ld, ld_out=ld)
+        out = torch.full((B * Ho * Wo, ld), 7.0, dtype=torch.float64)
+        E.call("nearest_add", **geom, a=_nhwc(a, ld, 1e30), src=_nhwc(src.detach(), ld, 1e30), out=out)
+        assert _close(out[:, :C], _nhwc(ref.detach()), 1e-6 if bf16 else 1e-10) and float((out[:, C:] - 7.0).abs().max() if ld > C else 0.0) == 0.0
+        buf = _nhwc(a, ld, 7.0)                                                                   # in place: out = a
+        E.call("nearest_add", **geom, a=buf, src=_nhwc(src.detach(), ld, 1e30), out=buf)
+        assert torch.equal(buf, out)
+        ds = torch.full((B * Hi * Wi, ld), 7.0, dtype=torch.float64)
+        E.call("nearest_add_bwd", **geom, a=_nhwc(dy, ld, 1e30), src=None, out=ds)
+        assert _close(ds[:, :C], _nhwc(src.grad), 1e-6 if bf16 else 1e-10) and float((ds[:, C:] - 7.0).abs().max() if ld > C else 0.0) == 0.0
+
+
+def test_bbox_tail_fwd_bwd_vs_torch():
+    for seed, (B, H, W, dims, bbox2d, scales, pitch) in enumerate(((2, 5, 7, (2, 1, 3, 3, 4), 1, True, 8), (3, 4, 3, (2, 1, 3, 3), 0, True, 0), (2, 3, 5, (6,), 0, False, 8),
+                                                                 (2, 3, 5, (9, 1, 4), 1, True, 0))):
+        g = g_(90 + seed)
+        xs = [(0.5 * torch.randn(B, d, H, W, generator=g)).double().requires_grad_(True) for d in dims]
+        s = torch.tensor([0.9, 1.1, 0.7, 1.3]).double().requires_grad_(True)
+        bp = torch.cat(xs, 1)
+        nch = bp.shape[1]
+        if scales:
+            mid = nch - 4 if bbox2d else nch
+            parts = [bp[:, :2] * s[0], (bp[:, 2:3] * s[1]).exp(), (bp[:, 3:6] * s[2]).exp() + float(torch.tensor(1e-6, dtype=torch.float32)), bp[:, 6:mid]]
+            if bbox2d:
+                assert float((bp[:, mid:] * s[3]).detach().abs().min()) >= 1e-3
+                parts.append(F.relu(bp[:, mid:] * s[3]))
+            ref = torch.cat(parts, 1)
+        else:
+            ref = bp * 1.0
+        dy = torch.randn(ref.shape, generator=g).double()
+        ref.backward(dy)
+        ldx = [pitch or d for d in dims]
+        geom = dict(x=[_nhwc(x.detach(), l, 1e30) for x, l in zip(xs, ldx)], ldx=ldx, dims=list(dims), ngroups=len(dims), scales=s.detach() if scales else None,
+                    bbox2d=bbox2d, B=B, H=H, W=W)
+        out = torch.full((B, nch, H, W), 7.0, dtype=torch.float64)
+        E.call("fcos_bbox_post", **geom, out=out)
+        assert _close(out, ref.detach())
+        dxs = [torch.full((B * H * W, l), 7.0, dtype=torch.float64) for l in ldx]
+        dxs[-1] = None if len(dims) > 1 else dxs[-1]
+        dsc = torch.full((4,), 9.0, dtype=torch.float64)
+        E.call("fcos_bbox_post_bwd", **geom, dout=dy, dx=dxs, dscales=dsc if scales else None)
+        for x, d, dxg in zip(xs, dims, dxs):
+            if dxg is not None:
+                assert _close(dxg[:, :d], _nhwc(x.grad)) and float(dxg[:, d:].abs().max() if dxg.shape[1] > d else 0.0) == 0.0
+        if scales:
+            assert _close(dsc, s.grad)
+        else:
+            assert float((dsc - 9.0).abs().max()) == 0.0

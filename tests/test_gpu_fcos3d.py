@@ -1,7 +1,7 @@
 """-m gpu: the FCOS3D criterion (det_model.DetModel, csrc/det_loss3d.hip) against the unmodified reference (tests/golden/fcos3d.*,
 make_fcos3d_golden.py) and the plain-torch restatement tests/fcos3d_ref.py: labels bit for bit, the eight components, loss_sum, every map
 gradient, the mini_det head chain, run-to-run bitwise reproducibility, no host synchronisation, FusedMultiTaskLoss with '3ddet', and
-the cs geometry."""
+the cs geometry, more than 128 gts per image."""
 import json
 import os
 
@@ -188,6 +188,55 @@ def test_cs_geometry_matches_the_restatement():
         assert _rel(float(ld[k]), float(rd[k])) < 1e-5, (k, float(ld[k]), float(rd[k]))
     assert _rel(float(ls), float(rs)) < 1e-5
     print(f"cs geometry B=2: num_pos {num_pos}, " + ", ".join(f"{k} {float(v):.4f}" for k, v in ld.items()))
+
+
+MANY_LEVELS = ((12, 20), (6, 10), (3, 5))
+
+
+@pytest.mark.gpu
+def test_more_than_128_gts_per_image_match_the_restatement():
+    """fcos3d_fwd_kernel stages the gts in LDS 128 at a time: 128 (one full batch), 129 (a one-gt second batch) and 300 gts (three batches,
+    ragged last) on three small levels, B = 3.  Labels identical to the fp32 restatement, components and loss_sum within 1e-5 of its fp64
+    losses (the cs-geometry bound), every map gradient within 1e-5 * max|ref| of its fp64 autograd (the fixture test's bound)."""
+    _need_gpu()
+    import mtt_amd
+    dm = mtt_amd.det_model
+    params = dm.cs_det_model_params()
+    params.update(strides=[8, 16, 32], regress_ranges=((-1, 48), (48, 96), (96, dm.INF)))
+    p = {"IMAGE_ORI_SIZE": (96, 160), "TRAIN": {"SCALE": (96, 160)}, "img_ds_ratio": 1.0}
+    dm.configure_3ddet(p, params)
+    crit, B = p["detmodel"], 3
+    labels = dm.synthetic_det_labels(B, (96, 160), (128, 129, 300), seed=9)
+    g = torch.Generator().manual_seed(10)
+    preds = [[(torch.randn(B, ch, h, w, generator=g) * (2.0 if k == 0 else 1.0)) for h, w in MANY_LEVELS] for k, ch in enumerate((6, 13, 6, 1))]
+    dists = []
+    keep, lab, _, _ = fcos3d_ref.assign(p["det_model_params"], labels, MANY_LEVELS, dists_out=dists)
+    assert keep == [0, 1, 2] and [d.shape[1] for d in dists] == [128, 129, 300]
+    for d in dists:                                            # no point has two gts at its minimum distance: the argmin is unambiguous
+        two = torch.topk(d, 2, dim=1, largest=False)[0]
+        assert bool(((two[:, 0] < two[:, 1]) | (two[:, 0] == fcos3d_ref.INF)).all())
+    pts = crit.get_points(MANY_LEVELS, torch.float32, DEV)
+    dl = labels["det_labels"]
+    glab, _, _ = crit.get_targets(pts, [e["bbox_modal"] for e in dl], [e["label"] for e in dl],
+                                  [torch.cat([e["center_S"], e["size_S"], e["rotation_S"]], 1) for e in dl], [e["label"] for e in dl],
+                                  [e["center_I"][:, :2] for e in dl], [e["center_I"][:, 2] for e in dl])
+    offs = np.cumsum([0] + [h * w for h, w in MANY_LEVELS])
+    ref = torch.cat([lab[:, offs[l]:offs[l + 1]].reshape(-1) for l in range(len(MANY_LEVELS))])
+    assert torch.equal(torch.cat(glab).cpu(), ref), int((torch.cat(glab).cpu() != ref).sum())
+    num_pos = int((ref < 6).sum())
+    assert num_pos > 0
+    leaves = [[m.to(DEV).requires_grad_(True) for m in lst] for lst in preds]
+    ld, ls = crit.loss(leaves, labels)
+    rleaves = [[m.double().requires_grad_(True) for m in lst] for lst in preds]
+    rd, rs = fcos3d_ref.loss(p["det_model_params"], rleaves, labels)
+    for k in rd:
+        assert _rel(float(ld[k]), float(rd[k])) < 1e-5, (k, float(ld[k]), float(rd[k]))
+    assert _rel(float(ls), float(rs)) < 1e-5
+    grads = torch.autograd.grad(ls, [m for lst in leaves for m in lst])
+    rgrads = torch.autograd.grad(rs, [m for lst in rleaves for m in lst])
+    for j, (gg, rg) in enumerate(zip(grads, rgrads)):
+        assert float((gg.cpu().double() - rg).abs().max()) <= 1e-5 * max(float(rg.abs().max()), 1e-30), j
+    print(f"3 levels, gts (128, 129, 300): num_pos {num_pos}")
 
 
 @pytest.mark.gpu

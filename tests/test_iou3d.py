@@ -3,7 +3,8 @@
 CPU: the restatement oracle/iou3d_oracle.py against tests/golden/iou3d.npz — outputs of the REFERENCE's own device functions compiled
 for the host (tests/golden/make_iou3d_golden.py) — and, when /root/reference is present, against a fresh build of them; the host-side
 mirror of iou3d_utils.py on the ABI emulator.  GPU (-m gpu): the HIP kernels against the same goldens, against properties that hold at
-any size (IoU(a, a) = 1, symmetry, overlap <= min area, NMS idempotence, kept boxes mutually below the threshold) and at 4 096 boxes."""
+any size (IoU(a, a) = 1, symmetry, overlap <= min area, NMS idempotence, kept boxes mutually below the threshold), at 4 096 boxes, and at
+4 161 boxes (66 column blocks) against a host greedy pass.  The kernels' parity cases are gpu_cases.iou3d_cases()."""
 import os
 
 import numpy as np
@@ -134,3 +135,51 @@ def test_hip_properties_at_scale():
     kk = mtt_amd.iou3d.boxes_iou_bev(bx[keep], bx[keep])
     kk.fill_diagonal_(0)
     assert float(kk.max()) <= 0.3 + 1e-4                                                     # kept boxes are mutually below the threshold
+
+
+def _greedy(sup):
+    """The greedy pass over a suppression matrix (sup[i, j]: box i suppresses box j), boxes in score order -> kept indices."""
+    n = len(sup)
+    removed = np.zeros(n, bool)
+    keep = []
+    for i in range(n):
+        if not removed[i]:
+            keep.append(i)
+            removed[i + 1:] |= sup[i, i + 1:]
+    return np.array(keep, dtype=np.int64)
+
+
+def _axis_iou_f32(bx):
+    """iou_axis of csrc/iou3d.hip on every pair, in fp32 with its operation order (numpy rounds every operation, no contraction)."""
+    f = np.float32
+    a, b = bx[:, None, :], bx[None, :, :]
+    w = np.maximum(np.minimum(a[..., 2], b[..., 2]) - np.maximum(a[..., 0], b[..., 0]), f(0))
+    h = np.maximum(np.minimum(a[..., 3], b[..., 3]) - np.maximum(a[..., 1], b[..., 1]), f(0))
+    inter = w * h
+    area = (bx[:, 2] - bx[:, 0]) * (bx[:, 3] - bx[:, 1])
+    return inter / np.maximum((area[:, None] + area[None, :]) - inter, f(1e-8))
+
+
+@pytest.mark.gpu
+def test_hip_nms_over_more_than_64_column_blocks():
+    """4 161 boxes = 66 column blocks, the last of one box: nms_reduce_kernel's lanes take a second trip over the mask words of a row
+    (4 096 boxes are exactly 64 words).  Rotated: the kept set equals a host greedy pass over the device's own boxes_iou_bev matrix — both
+    kernels evaluate the same iou_rot with contraction off, so the comparison is exact.  Axis-aligned: the matrix is computed on the
+    host in fp32 in the kernel's operation order; no pair lies within 1e-4 of the threshold."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import mtt_amd
+    from tests.golden.make_iou3d_golden import boxes
+    n, thr = 4161, 0.3
+    bx = boxes(np.random.default_rng(4222), n, 0.9 * n ** 0.5)
+    gb = torch.from_numpy(bx).cuda()
+    scores = torch.linspace(1.0, 0.0, n).cuda()
+    iou = mtt_amd.iou3d.boxes_iou_bev(gb, gb).cpu().numpy()
+    want = _greedy(iou > np.float32(thr))
+    got = mtt_amd.iou3d.nms_gpu(gb, scores, thr).cpu().numpy()
+    assert 0 < len(want) < n and np.array_equal(got, want), (len(got), len(want))
+    iou = _axis_iou_f32(bx)
+    assert iou.dtype == np.float32 and not (np.abs(np.triu(iou, 1) - np.float32(thr)) < 1e-4).any()
+    want = _greedy(iou > np.float32(thr))
+    got = mtt_amd.iou3d.nms_normal_gpu(gb, scores, thr).cpu().numpy()
+    assert 0 < len(want) < n and np.array_equal(got, want), (len(got), len(want))

@@ -1,6 +1,6 @@
 """Host meta-test of the kernel parity comparator (gpu_cases.compare) over every case of gpu_cases.all_cases(): the emulator run on a
 copy of the case's storages stands in for the device.  The comparator must pass that copy and a copy with one-ulp bf16 moves, and must
-fail each planted defect: a wrong element (D1), a stray write (D2), a row read one row stride off (D3), a dropped lo plane (D4).
+fail each planted defect: a wrong element (D1; an integer element moved by at least 1), a stray write (D2), a row read one row stride off (D3), a dropped lo plane (D4).
 A per-case `elem` override loose enough to let D1 through fails here.  Also: the output buffers are sentinel-filled (no zero outside
 the written set of a storage the emulator writes) and every C-ABI entry point is covered by a parity case or a named device test."""
 import ast
@@ -138,6 +138,8 @@ def test_comparator_passes_the_emulator_and_fails_planted_defects(case):
         p = int(pos[torch.randint(pos.numel(), (1,), generator=gen)])
         e = g[p].double()
         delta = frac * s if s > 0 else 2.0 ** -126
+        if not g.is_floating_point():
+            delta = max(delta, 1.0)                 # an integer storage (NMS keep / num_out): the smallest move there is
         if g.dtype == torch.bfloat16 and key not in lo_planes:
             delta += 3 * float(gpu_cases.ulp_bf16(e.reshape(1)))
         old = g[p].clone()
