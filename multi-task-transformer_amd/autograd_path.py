@@ -327,8 +327,8 @@ class AttnHalfFn(Function):
         if split:
             xs, mean, rstd = ops.layernorm(XT, g1, b1, eps, prec, save_stats=True, out_dtype="split")
             xp32 = ops.prompt_rows32(xs, B, N, T, C) if chan else None      # the prompt rows (fp32-class) of the channel attention's Linears
-            wq = ops.pack_linear_split([Wqkv], tag + ('qkv',))
-            wp = ops.pack_linear_split([Wproj], tag + ('proj',))
+            wq = ops.pack_linear([Wqkv], prec, tag + ('qkv',), split=True)
+            wp = ops.pack_linear([Wproj], prec, tag + ('proj',), split=True)
             qkv = ops.linear(xs, wq, 3 * C, prec, bias=bqkv[None], out_dtype="split")[0]
             ao, rawlog, lse = ops.attention(qkv, B, N, nH, T, prec, want_lse=True)
             xn_b, xn_c = xs.hi, xs                  # backward operand: the bf16 hi plane; the channel attention reads the planes (no fp32 copy)
@@ -440,8 +440,8 @@ class MlpHalfFn(Function):
         # rounds 3-5 (multiples of 64), for A/B runs
         split = prec.split and ((C % 64 == 0 and Hd % 64 == 0) if MLP_SPLIT_RULE64 else (ops.split_gemm_ok(C) and ops.split_gemm_ok(Hd)))
         xn2, mean, rstd = ops.layernorm(XT2, g2, b2n, eps, prec, save_stats=True, out_dtype="split" if split else None)
-        w1 = ops.pack_linear_split([W1], tag + ('fc1',)) if split else ops.pack_linear([W1], prec, tag + ('fc1',))
-        w2 = ops.pack_linear_split([W2], tag + ('fc2',)) if split else ops.pack_linear([W2], prec, tag + ('fc2',))
+        w1 = ops.pack_linear([W1], prec, tag + ('fc1',), split=split)
+        w2 = ops.pack_linear([W2], prec, tag + ('fc2',), split=split)
         # what the backward's GELU' needs.  fp32-class backward (x3): the pre-activation z in fp32, GELU'(z) evaluated in the fc2 dgrad
         # epilogue.  bf16 backward (bf16, x3f): GELU'(z) itself, taken HERE where z is in registers in fp32 and stored as bf16 (the same
         # bytes as bf16(z)) — the fc2 dgrad epilogue is then one multiply per element instead of an erf + exp evaluation on 64 890 x 4 096
@@ -569,12 +569,8 @@ class BLinearFn(Function):
         if auto:
             sp = ops.split_cast(x.view(-1, x.shape[-1]))
             xin = ops.Split(sp.hi.view(x.shape), sp.lo.view(x.shape))
-        if xlo is not None or auto:
-            wpack = ops.pack_linear_split(list(ws), tag) if kmap is None else ops.pack_kmap_split(list(ws), N, kmap[0], kmap[1], tag)
-        elif kmap is None:
-            wpack = ops.pack_linear(list(ws), prec, tag)
-        else:
-            wpack = ops.pack_kmap(list(ws), N, kmap[0], kmap[1], prec, tag)
+        split = xlo is not None or auto
+        wpack = ops.pack_linear(list(ws), prec, tag, split=split) if kmap is None else ops.pack_kmap(list(ws), N, kmap[0], kmap[1], prec, tag, split=split)
         bias = ops.stack_vec(list(bs), (tag, 'b'))
         M, Np = x.shape[-2], pitch(N)
         if layout == 'catpair':
@@ -668,14 +664,14 @@ class Conv3x3Fn(Function):
         bias = ops.stack_vec(list(bs), (tag, 'b')) if has_bias else None
         xdt = x.dtype
         if xlo is not None:
-            y = ops.conv3x3(ops.Split(x, xlo), ops.pack_conv3_split(list(ws), tag), Co, Ci, B, H, W, prec, dil=dil, bias=bias, out_dtype=torch.float32)
+            y = ops.conv3x3(ops.Split(x, xlo), ops.pack_conv3(list(ws), prec, tag, split=True), Co, Ci, B, H, W, prec, dil=dil, bias=bias, out_dtype=torch.float32)
         elif prec.split and x.dtype == torch.float32 and ops.split_conv_ok(Ci, Co):
             # x3f on an fp32 input (head convs, Swin, InvPT): split it HERE, so that the hi plane — the bf16 operand the backward needs
             # anyway — is what gets saved instead of the fp32 activation plus a second cast pass in the backward
             Zx, rows, Cp = x.shape
             sp = ops.split_cast(x.contiguous().view(Zx * rows, Cp))
             xs = ops.Split(sp.hi.view(Zx, rows, Cp), sp.lo.view(Zx, rows, Cp))
-            y = ops.conv3x3(xs, ops.pack_conv3_split(list(ws), tag), Co, Ci, B, H, W, prec, dil=dil, bias=bias)
+            y = ops.conv3x3(xs, ops.pack_conv3(list(ws), prec, tag, split=True), Co, Ci, B, H, W, prec, dil=dil, bias=bias)
             x = xs.hi
         else:
             y = ops.conv3x3(x, ops.pack_conv3(list(ws), prec, tag), Co, Ci, B, H, W, prec, dil=dil, bias=bias)
@@ -745,7 +741,7 @@ class UpConv3x3Fn(Function):
             Zs, M, Kp = xa.shape
             sp = ops.split_cast(xa.reshape(Zs * M, Kp))
             xs = ops.Split(sp.hi.view(Zs, M, Kp), sp.lo.view(Zs, M, Kp))
-            w9 = ops.pack_upconv9_split(list(ws), tag)
+            w9 = ops.pack_upconv9(list(ws), prec, tag, split=True)
             y = ops.upconv3x3(xs, w9, Co, B, h, w, prec, bias=ops.stack_vec(list(bs), (tag, 'b')))
             ctx.save_for_backward(xs.hi, w9.hi)
         else:

@@ -89,6 +89,19 @@ def train_forward(x, C, bns, act, gammas=None, betas=None):
     return y, mean, rstd, scale
 
 
+def fold(bns, conv_biases, tag):
+    """eval BatchNorm folded into the producing conv's epilogue: scale = g/sqrt(v+eps), shift = b + (cb - m)*scale (conv_biases None: cb = 0)."""
+    def build():
+        with torch.no_grad():
+            sc = torch.stack([bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps) for bn in bns])
+            sh = torch.stack([bn.bias.detach() - bn.running_mean * s for bn, s in zip(bns, sc)])
+            if conv_biases is not None:
+                sh = sh + torch.stack([b.detach() for b in conv_biases]) * sc
+            return sc.contiguous(), sh.contiguous()
+    prm = [q for bn in bns for q in (bn.weight, bn.bias, bn.running_mean, bn.running_var)] + list(conv_biases or [])
+    return ops._cached((tag, tuple(id(q) for q in prm)), prm, build)
+
+
 def sync_backward_sums(s, bns):
     """s [2, Z, C] local sums of du and du*xhat -> summed over ranks (one all_reduce per stage)."""
     if _world(bns) > 1:

@@ -91,7 +91,7 @@ class SampledConvFn(Function):
         if om is not None:
             offs = dict(offset=om, ld_off=om.shape[-1], mask=om[:, 18:], ld_mask=om.shape[-1], mask_sigmoid=1, off_dtype=_dt(om))
         ops.call("dcn_im2col", x=x, x_dtype=_dt(x), col=ops._hi(col), col_lo=col.lo if split else None, col_dtype=_dt(col), **g, **offs)
-        wpack = ops.pack_conv3_split([weight], tag) if split else ops.pack_conv3([weight], prec, tag)
+        wpack = ops.pack_conv3([weight], prec, tag, split=split)
         y = ops.linear(col, wpack, Co, prec, bias=ops.stack_vec([bias], (tag, 'b')) if bias is not None else None)[0]
         ctx.save_for_backward(x, om, ops._hi(col), weight)
         ctx.meta = (geo, prec, tag, bias is not None)

@@ -23,6 +23,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
+from . import bn as bn_mod
 from . import ops
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, F32, OP_K, OP_R, dtype_code
 from .taskprompter import Mlp, PatchEmbed, _init_vit_weights, _prec_of, trunc_normal_
@@ -108,7 +109,9 @@ class VisionTransformer(nn.Module):
         # x3f: the four big Linears of a block on the split-plane LDS-DMA kernel (operands written as hi / lo planes by LayerNorm, the
         # qkv / fc1 epilogues and the attention kernel), as TaskPrompter._block_split; the K = C reductions must be whole 32-deep steps
         split = prec.split and C % 32 == 0
-        pack = (lambda ws, tg: ops.pack_linear_split(ws, tg)) if split else (lambda ws, tg: ops.pack_linear(ws, prec, tg))
+
+        def pack(ws, tg):
+            return ops.pack_linear(ws, prec, tg, split=split)
         sp = dict(out_dtype="split") if split else {}
         for i, blk in enumerate(self.blocks):
             tag = ('vblk', i)
@@ -251,24 +254,6 @@ class MLPHead(nn.Module):
         self.linear_pred = nn.Conv2d(in_channels, num_classes, kernel_size=1)
 
 
-def _fold(bns, conv_biases, tag):
-    def build():
-        with torch.no_grad():
-            sc = torch.stack([bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps) for bn in bns])
-            sh = torch.stack([bn.bias.detach() - bn.running_mean * s for bn, s in zip(bns, sc)])
-            if conv_biases is not None:
-                sh = sh + torch.stack([b.detach() for b in conv_biases]) * sc
-            return sc.contiguous(), sh.contiguous()
-    prm = [q for bn in bns for q in (bn.weight, bn.bias, bn.running_mean, bn.running_var)] + list(conv_biases or [])
-    return ops._cached((tag, tuple(id(q) for q in prm)), prm, build)
-
-
-def _bn_train(y, bns, C, act):
-    """train-mode BatchNorm (+act) on [Z, rows, ld]; updates running statistics (momentum 0.1)."""
-    from . import bn as bn_mod
-    return bn_mod.train_forward(y, C, list(bns), act)[0]
-
-
 class TransformerDecoder(nn.Module):
     """transformer_decoder.py:18-98 + InvPT.forward (invpt.py:502-544)."""
 
@@ -351,12 +336,12 @@ class TransformerDecoder(nn.Module):
         W1 = ops.pack_conv3([m[1].conv.weight for m in pd], prec, 'pd1')
         xin = x.expand(T, rows0, x.shape[-1])
         if training:
-            y = _bn_train(ops.conv3x3(xin, W0, C, C, B, mh, mw, prec), [m[0].bn1 for m in pd], C, ACT_RELU)
-            y = _bn_train(ops.conv3x3(y, W1, Ed, C, B, mh, mw, prec), [m[1].bn1 for m in pd], Ed, ACT_RELU)
+            y = bn_mod.train_forward(ops.conv3x3(xin, W0, C, C, B, mh, mw, prec), C, [m[0].bn1 for m in pd], ACT_RELU)[0]
+            y = bn_mod.train_forward(ops.conv3x3(y, W1, Ed, C, B, mh, mw, prec), Ed, [m[1].bn1 for m in pd], ACT_RELU)[0]
         else:
-            sc, sh = _fold([m[0].bn1 for m in pd], None, 'pd0bn')
+            sc, sh = bn_mod.fold([m[0].bn1 for m in pd], None, 'pd0bn')
             y = ops.conv3x3(xin, W0, C, C, B, mh, mw, prec, bias=sh, colscale=sc, act=ACT_RELU)
-            sc, sh = _fold([m[1].bn1 for m in pd], None, 'pd1bn')
+            sc, sh = bn_mod.fold([m[1].bn1 for m in pd], None, 'pd1bn')
             y = ops.conv3x3(y, W1, Ed, C, B, mh, mw, prec, bias=sh, colscale=sc, act=ACT_RELU)
         Edp = pitch(Ed)
         inter, xs = {}, []
@@ -393,12 +378,12 @@ class TransformerDecoder(nn.Module):
                 Wc1 = ops.pack_conv3([m[1].weight for m in ue], prec, ('ue1', i))
                 Wc2 = ops.pack_conv3([m[4].weight for m in ue], prec, ('ue2', i))
                 if training:
-                    yy = _bn_train(ops.conv3x3(up, Wc1, D, Din, B, gh, gw, prec, dil=2), [m[2] for m in ue], D, ACT_RELU)
-                    yy = _bn_train(ops.conv3x3(yy, Wc2, D, D, B, gh, gw, prec, dil=2), [m[5] for m in ue], D, ACT_RELU)
+                    yy = bn_mod.train_forward(ops.conv3x3(up, Wc1, D, Din, B, gh, gw, prec, dil=2), D, [m[2] for m in ue], ACT_RELU)[0]
+                    yy = bn_mod.train_forward(ops.conv3x3(yy, Wc2, D, D, B, gh, gw, prec, dil=2), D, [m[5] for m in ue], ACT_RELU)[0]
                 else:
-                    sc, sh = _fold([m[2] for m in ue], None, ('ue1bn', i))
+                    sc, sh = bn_mod.fold([m[2] for m in ue], None, ('ue1bn', i))
                     yy = ops.conv3x3(up, Wc1, D, Din, B, gh, gw, prec, dil=2, bias=sh, colscale=sc, act=ACT_RELU)
-                    sc, sh = _fold([m[5] for m in ue], None, ('ue2bn', i))
+                    sc, sh = bn_mod.fold([m[5] for m in ue], None, ('ue2bn', i))
                     yy = ops.conv3x3(yy, Wc2, D, D, B, gh, gw, prec, dil=2, bias=sh, colscale=sc, act=ACT_RELU)
                 skip = back1 if i == 1 else back0                                           # invpt.py:406-411
                 X = yy
@@ -428,9 +413,9 @@ class TransformerDecoder(nn.Module):
         Wm = ops.pack_conv3([m[0].weight for m in mps], prec, 'mtp')
         if training:
             f = ops.conv3x3(accq, Wm, E, E, B, th, tw, prec, bias=ops.stack_vec([m[0].bias for m in mps], 'mtpb'))
-            f = _bn_train(f, [m[1] for m in mps], E, ACT_RELU)
+            f = bn_mod.train_forward(f, E, [m[1] for m in mps], ACT_RELU)[0]
         else:
-            sc, sh = _fold([m[1] for m in mps], [m[0].bias for m in mps], 'mtpbn')
+            sc, sh = bn_mod.fold([m[1] for m in mps], [m[0].bias for m in mps], 'mtpbn')
             f = ops.conv3x3(accq, Wm, E, E, B, th, tw, prec, bias=sh, colscale=sc, act=ACT_RELU)
         return f, inter
 
@@ -461,9 +446,9 @@ class TransformerDecoder(nn.Module):
         bns = [m.bn for m in at.conv_proj_q]
         if self.training:
             ops.call("dwconv3x3s2", x=xn, w=wq, y=qmap, scale=None, shift=None, Z=T, B=B, H=gh, W=gw, ld=Dp, dtype=dtype_code(xn))
-            qmap = _bn_train(qmap, bns, D, ACT_NONE)
+            qmap = bn_mod.train_forward(qmap, D, list(bns), ACT_NONE)[0]
         else:
-            sc, sh = _fold(bns, None, ('dwqbn', si))
+            sc, sh = bn_mod.fold(bns, None, ('dwqbn', si))
             scp, shp = self._pad_cols(sc, Dp), self._pad_cols(sh, Dp)
             ops.call("dwconv3x3s2", x=xn, w=wq, y=qmap, scale=scp, shift=shp, Z=T, B=B, H=gh, W=gw, ld=Dp, dtype=dtype_code(xn))
         kvmap = torch.empty(T, B * nk, Dp, dtype=prec.adt, device=dev)

@@ -22,13 +22,11 @@ PITCH32_FROM = 160         # channel counts >= this take a pitch that is a multi
 
 
 def pitch(n):
-    """The channel pitch of a map with n channels (`pad8` until round 6, when every pitch was the next multiple of 8): the next multiple of 8 — of 32 from PITCH32_FROM channels on, so that the K loop of a GEMM or
+    """The channel pitch of a map with n channels: the next multiple of 8 — of 32 from PITCH32_FROM channels on, so that the K loop of a GEMM or
     3x3 implicit GEMM reading the map is whole 32-deep LDS-DMA steps (176 -> 192, 232 -> 256, 456 -> 480, 784 -> 800: the split-plane / ring
-    kernels instead of the register-staged ones).  Every kernel writes the channels C..ld-1 of its output maps as zeros."""
+    kernels instead of the register-staged ones).  Every kernel writes the channels C..ld-1 of its output maps as zeros.  PITCH32_FROM may
+    be assigned at run time (A/B runs, the suite's wide-pitch leg): it is part of every pack key (_cached, seg_pack)."""
     return (n + 31) // 32 * 32 if n >= PITCH32_FROM else (n + 7) // 8 * 8
-
-
-pad8 = pitch               # historical name (tools / tests)
 
 
 DEFAULT_PREC = "x3f"        # arithmetic mode of a model whose config does not name one (`p.mtt_prec`): the tolerance-compliant mode
@@ -147,7 +145,8 @@ def _epoch_touched(old_epoch, ptrs):
 
 
 def _cached(key, params, build):
-    """Pack cache keyed by `key`, valid while every source tensor is the same object with the same storage and version."""
+    """Pack cache keyed by `key` and the pitch rule, valid while every source tensor is the same object with the same storage and version."""
+    key = (key, PITCH32_FROM)
     ver = (_param_epoch, tuple((p.data_ptr(), p._version) for p in params))
     hit = _pack_cache.get(key)
     if hit is not None and hit[0] == ver and all(r() is p for r, p in zip(hit[2], params)):
@@ -192,9 +191,10 @@ def pack_matrix(w2d, prec):
 _ITEM = {torch.float32: 4, torch.bfloat16: 2}
 
 
-def segment(src, src_off, dst, dst_off, n, s, d, dst_lo=None):
+def segment(src, src_off, dst, dst_off, n, s, d):
     """One mtt_segcopy segment: the box n = (n0, n1, n2) read from `src` (tensor, element offset src_off, element strides s) and written to
-    `dst` (element offset dst_off, strides d; `dst_lo` = the lo plane of a Split destination).  Strides of singleton dimensions are ignored."""
+    `dst` (tensor, or Split: both planes; element offset dst_off, strides d).  Strides of singleton dimensions are ignored."""
+    dst, dst_lo = (dst.hi, dst.lo) if isinstance(dst, Split) else (dst, None)
     n = tuple(int(v) for v in n)
     s = tuple(int(v) if k > 1 else 0 for v, k in zip(s, n))
     d = tuple(int(v) if k > 1 else 0 for v, k in zip(d, n))
@@ -318,8 +318,10 @@ def seg_pack(key, params, alloc, rows_of, check=None):
     """Persistent pack `key` of the parameters `params`: `alloc()` -> zero-initialised destination (tensor or Split), `rows_of(value)` ->
     its segcopy rows.  Served from the registry while the parameters are unchanged; after a parameter update the FIRST stale lookup
     refreshes every registered pack in one launch (mtt_segcopy), so a training step re-packs all weights with one kernel instead of one
-    cast / copy per weight.  Padding (outside the boxes) is written once, by `alloc`."""
+    cast / copy per weight.  Padding (outside the boxes) is written once, by `alloc`.  The pitch rule is part of the key: the layouts
+    below follow pitch(), so a pack built under another PITCH32_FROM is another entry."""
     global _packs_gen
+    key = (key, PITCH32_FROM)
     ver = _pver(params)
     e = _packs.get(key)
     if e is not None and len(e.params) == len(params) and all(r() is p for r, p in zip(e.params, params)) \
@@ -399,14 +401,28 @@ def _check_sources(weights, ok):
                              ".contiguous().float() on the module's parameters)")
 
 
-def pack_linear(weights, prec, tag):
-    """List of Z parameters [N, K] (or 1x1 conv [N, K, 1, 1]) -> one [Z, N, Kp] buffer in the activation dtype (zero padded)."""
+def _dest(shape, dtype, device):
+    """zero-initialised pack destination: a tensor of `dtype`, or hi / lo planes for dtype 'split'."""
+    if dtype == 'split':
+        return Split(torch.zeros(shape, dtype=torch.bfloat16, device=device), torch.zeros(shape, dtype=torch.bfloat16, device=device))
+    return torch.zeros(shape, dtype=dtype, device=device)
+
+
+def _mode(prec, split):
+    """(key component, destination dtype) of a pack: pre-split planes and the activation-dtype pack of one tag are distinct entries."""
+    return ('split', 'split') if split else (prec.name, prec.adt)
+
+
+def pack_linear(weights, prec, tag, split=False):
+    """List of Z parameters [N, K] (or 1x1 conv [N, K, 1, 1]) -> one [Z, N, Kp] buffer in the activation dtype (zero padded); split=True:
+    Split [Z, N, Kp], pre-split weight planes for the LDS-DMA x3 GEMM (x3f mode)."""
     N, K = _w2d(weights[0])
     Kp, Z = pitch(K), len(weights)
-    if prec.adt == torch.float32 and Z == 1 and K == Kp and weights[0].is_contiguous():
+    if not split and prec.adt == torch.float32 and Z == 1 and K == Kp and weights[0].is_contiguous():
         return weights[0].detach().reshape(1, N, K)               # fp32 storage: the parameter itself is the operand
-    return seg_pack((tag, prec.name, tuple(id(w) for w in weights)), list(weights),
-                    lambda: torch.zeros(Z, N, Kp, dtype=prec.adt, device=weights[0].device),
+    mode, dt = _mode(prec, split)
+    return seg_pack((tag, mode, tuple(id(w) for w in weights)), list(weights),
+                    lambda: _dest((Z, N, Kp), dt, weights[0].device),
                     lambda buf: [segment(w, 0, buf, z * N * Kp, (1, N, K), (0, K, 1), (0, Kp, 1)) for z, w in enumerate(weights)],
                     check=lambda: _check_sources(weights, lambda w: _w2d(w) == (N, K)))
 
@@ -420,43 +436,22 @@ def pack_linear_T(weight, dtype, tag):
                     check=lambda: _check_sources([weight], lambda w: True))
 
 
-def pack_linear_split(weights, tag):
-    """List of Z parameters [N, K] -> Split [Z, N, pitch(K)]: pre-split weight planes for the LDS-DMA x3 GEMM (x3f mode)."""
-    N, K = _w2d(weights[0])
-    Kp, Z = pitch(K), len(weights)
-    dev = weights[0].device
-    return seg_pack((tag, 'split', tuple(id(w) for w in weights)), list(weights),
-                    lambda: Split(torch.zeros(Z, N, Kp, dtype=torch.bfloat16, device=dev), torch.zeros(Z, N, Kp, dtype=torch.bfloat16, device=dev)),
-                    lambda sp: [segment(w, 0, sp.hi, z * N * Kp, (1, N, K), (0, K, 1), (0, Kp, 1), dst_lo=sp.lo) for z, w in enumerate(weights)],
-                    check=lambda: _check_sources(weights, lambda w: _w2d(w) == (N, K)))
-
-
-def pack_conv3(weights, prec, tag, transpose=False):
+def pack_conv3(weights, prec, tag, transpose=False, split=None):
     """List of Z conv weights [Co, Ci, 3, 3] -> [Z, Co, 9*Cip] with k = tap*Cip + ci (taps row-major).
-    transpose=True packs the dgrad operand [Z, Ci, 9*Cop] with k = tap*Cop + co."""
+    transpose=True packs the dgrad operand [Z, Ci, 9*Cop] with k = tap*Cop + co (never as planes).
+    split: True -> pre-split planes (Split of the same shape) for the split-plane implicit-GEMM conv; None -> planes in the x3f forward
+    where that kernel applies (conv3x3 then runs it; an fp32 input is split by one pass first)."""
     Co, Ci = weights[0].shape[:2]
-    if prec.split and not transpose and split_conv_ok(Ci, Co):
-        # x3f forward: pre-split planes -> conv3x3 runs the split-plane implicit-GEMM kernel (an fp32 input is split by one pass first)
-        return pack_conv3_split(weights, tag)
+    if split is None:
+        split = prec.split and split_conv_ok(Ci, Co)
+    mode, dt = _mode(prec, split and not transpose)
     R, Cin = (Ci, Co) if transpose else (Co, Ci)
     Cp, Z = pitch(Cin), len(weights)
     # logical box (r, tap, c): source W[co, ci, tap] has strides (Ci*9, 9, 1) over (co, ci, tap)
     s = (9, 1, Ci * 9) if transpose else (Ci * 9, 1, 9)
-    return seg_pack((tag, prec.name, transpose, tuple(id(w) for w in weights)), list(weights),
-                    lambda: torch.zeros(Z, R, 9 * Cp, dtype=prec.adt, device=weights[0].device),
+    return seg_pack((tag, mode, 'conv3', transpose, tuple(id(w) for w in weights)), list(weights),
+                    lambda: _dest((Z, R, 9 * Cp), dt, weights[0].device),
                     lambda buf: [segment(w, 0, buf, z * R * 9 * Cp, (R, 9, Cin), s, (9 * Cp, Cp, 1)) for z, w in enumerate(weights)],
-                    check=lambda: _check_sources(weights, lambda w: tuple(w.shape) == (Co, Ci, 3, 3)))
-
-
-def pack_conv3_split(weights, tag):
-    """pack_conv3 as pre-split planes (Split [Z, Co, 9*pitch(Ci)], k = tap*Cip + ci) for the split-plane implicit-GEMM conv."""
-    Co, Ci = weights[0].shape[:2]
-    Cp, Z = pitch(Ci), len(weights)
-    dev = weights[0].device
-    return seg_pack((tag, 'split', 'conv3', tuple(id(w) for w in weights)), list(weights),
-                    lambda: Split(torch.zeros(Z, Co, 9 * Cp, dtype=torch.bfloat16, device=dev), torch.zeros(Z, Co, 9 * Cp, dtype=torch.bfloat16, device=dev)),
-                    lambda sp: [segment(w, 0, sp.hi, z * Co * 9 * Cp, (Co, 9, Ci), (Ci * 9, 1, 9), (9 * Cp, Cp, 1), dst_lo=sp.lo)
-                                for z, w in enumerate(weights)],
                     check=lambda: _check_sources(weights, lambda w: tuple(w.shape) == (Co, Ci, 3, 3)))
 
 
@@ -469,51 +464,29 @@ def split_conv_ok(Ci, Co=None):
     return Cp % 32 == 0 and Cp <= 4096 and (Co is None or Co * 9 * Cp < 2 ** 31)
 
 
-def pack_upconv9(weights, prec, tag):
+def pack_upconv9(weights, prec, tag, split=False):
     """List of Z conv weights [Co, Ci, 3, 3] -> [Z, 9*pitch(Co), pitch(Ci)]: row (ky*3+kx)*pitch(Co) + co holds W[co, :, ky, kx] — the nine
     tap matrices of the "taps first" form of upsample x4 + 3x3 conv (mtt_upconv_desc) stacked as ONE linear layer; rows of the channel
-    padding are zero, so its output planes carry zero padding channels."""
+    padding are zero, so its output planes carry zero padding channels.  split=True: pre-split planes for the split-plane GEMM."""
     Co, Ci = weights[0].shape[:2]
     Cop, Kp, Z = pitch(Co), pitch(Ci), len(weights)
-    return seg_pack((tag, prec.name, 'up9', tuple(id(w) for w in weights)), list(weights),
-                    lambda: torch.zeros(Z, 9 * Cop, Kp, dtype=prec.adt, device=weights[0].device),
+    mode, dt = _mode(prec, split)
+    return seg_pack((tag, mode, 'up9', tuple(id(w) for w in weights)), list(weights),
+                    lambda: _dest((Z, 9 * Cop, Kp), dt, weights[0].device),
                     lambda buf: [segment(w, 0, buf, z * 9 * Cop * Kp, (9, Co, Ci), (1, Ci * 9, 9), (Cop * Kp, Kp, 1)) for z, w in enumerate(weights)],
                     check=lambda: _check_sources(weights, lambda w: tuple(w.shape) == (Co, Ci, 3, 3)))
 
 
-def pack_upconv9_split(weights, tag):
-    """pack_upconv9 as pre-split planes (Split [Z, 9*pitch(Co), pitch(Ci)]) for the split-plane GEMM."""
-    Co, Ci = weights[0].shape[:2]
-    Cop, Kp, Z = pitch(Co), pitch(Ci), len(weights)
-    dev = weights[0].device
-    return seg_pack((tag, 'split', 'up9', tuple(id(w) for w in weights)), list(weights),
-                    lambda: Split(torch.zeros(Z, 9 * Cop, Kp, dtype=torch.bfloat16, device=dev), torch.zeros(Z, 9 * Cop, Kp, dtype=torch.bfloat16, device=dev)),
-                    lambda sp: [segment(w, 0, sp.hi, z * 9 * Cop * Kp, (9, Co, Ci), (1, Ci * 9, 9), (Cop * Kp, Kp, 1), dst_lo=sp.lo)
-                                for z, w in enumerate(weights)],
-                    check=lambda: _check_sources(weights, lambda w: tuple(w.shape) == (Co, Ci, 3, 3)))
-
-
-def pack_kmap(weights, N, Kp, kmap, prec, tag):
+def pack_kmap(weights, N, Kp, kmap, prec, tag, split=False):
     """List of Z parameters [N, K...] -> [Z, N, Kp] with the column ranges (dst0, src0, len) of `kmap` copied (inputs that are padded
-    concatenations: taskprompter.py:471 torch.cat([spa, chan], 1) feeding fea_fuse[0])."""
+    concatenations: taskprompter.py:471 torch.cat([spa, chan], 1) feeding fea_fuse[0]).  split=True: pre-split planes for the split-plane GEMM."""
     Z = len(weights)
     K = weights[0].numel() // N
-    return seg_pack((tag, prec.name, 'kmap', tuple(id(w) for w in weights)), list(weights),
-                    lambda: torch.zeros(Z, N, Kp, dtype=prec.adt, device=weights[0].device),
+    mode, dt = _mode(prec, split)
+    return seg_pack((tag, mode, 'kmap', tuple(id(w) for w in weights)), list(weights),
+                    lambda: _dest((Z, N, Kp), dt, weights[0].device),
                     lambda buf: [segment(w, s0, buf, z * N * Kp + d0, (1, N, ln), (0, K, 1), (0, Kp, 1))
                                  for z, w in enumerate(weights) for (d0, s0, ln) in kmap],
-                    check=lambda: _check_sources(weights, lambda w: w.numel() == N * K))
-
-
-def pack_kmap_split(weights, N, Kp, kmap, tag):
-    """pack_kmap as pre-split planes (Split [Z, N, Kp]) for the split-plane GEMM."""
-    Z = len(weights)
-    K = weights[0].numel() // N
-    dev = weights[0].device
-    return seg_pack((tag, 'split', 'kmap', tuple(id(w) for w in weights)), list(weights),
-                    lambda: Split(torch.zeros(Z, N, Kp, dtype=torch.bfloat16, device=dev), torch.zeros(Z, N, Kp, dtype=torch.bfloat16, device=dev)),
-                    lambda sp: [segment(w, s0, sp.hi, z * N * Kp + d0, (1, N, ln), (0, K, 1), (0, Kp, 1), dst_lo=sp.lo)
-                                for z, w in enumerate(weights) for (d0, s0, ln) in kmap],
                     check=lambda: _check_sources(weights, lambda w: w.numel() == N * K))
 
 

@@ -24,6 +24,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
+from . import bn as bn_mod
 from . import ops
 from ._lib import ACT_GELU, ACT_NONE
 
@@ -307,11 +308,11 @@ class TaskPrompter(nn.Module):
         hw = grid[0] * grid[1]
         a = blk.attn
         xs, _, _ = ops.layernorm(XT, blk.norm1.weight.detach(), blk.norm1.bias.detach(), blk.norm1.eps, prec, out_dtype="split")
-        qkv = ops.linear(xs, ops.pack_linear_split([a.qkv.weight], tag + ('qkv',)), 3 * C, prec, bias=a.qkv.bias.detach()[None],
+        qkv = ops.linear(xs, ops.pack_linear([a.qkv.weight], prec, tag + ('qkv',), split=True), 3 * C, prec, bias=a.qkv.bias.detach()[None],
                          out_dtype="split")[0]
         ao, rawlog, _ = ops.attention(qkv, B, N, nH, T, prec)
         XT2 = torch.empty_like(XT)
-        ops.linear(ao, ops.pack_linear_split([a.proj.weight], tag + ('proj',)), C, prec, bias=a.proj.bias.detach()[None], out=XT2, resid=XT)
+        ops.linear(ao, ops.pack_linear([a.proj.weight], prec, tag + ('proj',), split=True), C, prec, bias=a.proj.bias.detach()[None], out=XT2, resid=XT)
         # channel attention: its patch rows are read as the planes LayerNorm wrote (no fp32 copy of the normalised tokens), its T prompt rows
         # per image are gathered into a small fp32 matrix
         cq = ops.linear(ops.prompt_rows32(xs, B, N, T, C), ops.pack_linear([a.token_trans.weight], prec, tag + ('tt',)), hw, prec,
@@ -321,10 +322,10 @@ class TaskPrompter(nn.Module):
         ops.linear(cq, ops.pack_linear([a.token_trans1.weight], prec, tag + ('tt1',)), C, prec,
                    bias=a.token_trans1.bias.detach()[None], out=pr, d_rows=(T, N * C, C), resid=pr, M=B * T)
         xs2, _, _ = ops.layernorm(XT2, blk.norm2.weight.detach(), blk.norm2.bias.detach(), blk.norm2.eps, prec, out_dtype="split")
-        hmid = ops.linear(xs2, ops.pack_linear_split([blk.mlp.fc1.weight], tag + ('fc1',)), 4 * C, prec,
+        hmid = ops.linear(xs2, ops.pack_linear([blk.mlp.fc1.weight], prec, tag + ('fc1',), split=True), 4 * C, prec,
                           bias=blk.mlp.fc1.bias.detach()[None], act=ACT_GELU, out_dtype="split")[0]
         XT3 = torch.empty_like(XT)
-        ops.linear(hmid, ops.pack_linear_split([blk.mlp.fc2.weight], tag + ('fc2',)), C, prec,
+        ops.linear(hmid, ops.pack_linear([blk.mlp.fc2.weight], prec, tag + ('fc2',), split=True), C, prec,
                    bias=blk.mlp.fc2.bias.detach()[None], out=XT3, resid=XT2)
         return XT3, rawlog, rawchan
 
@@ -342,20 +343,17 @@ class TaskPrompter(nn.Module):
         bdec = ops.stack_vec(dec_b, ('decb', il))
         f0 = [self.fea_fuse[il][t][0].weight for t in names]
         # fea_fuse[0] reads torch.cat([spa, chan], 1) (:471): its K = 2*tar columns land at 0 and pitch(tar) of the padded concatenation
-        if self._decoder_split():
-            Wdec = ops.pack_linear_split(dec_w, ('dec', il))
-            W0 = ops.pack_kmap_split(f0, F, 2 * tarp, [(0, 0, tar), (tarp, tar, tar)], ('f0', il))
-        else:
-            Wdec = ops.pack_linear(dec_w, prec, ('dec', il))
-            W0 = ops.pack_kmap(f0, F, 2 * tarp, [(0, 0, tar), (tarp, tar, tar)], pf, ('f0', il))
+        sp = self._decoder_split()
+        Wdec = ops.pack_linear(dec_w, prec, ('dec', il), split=sp)
+        W0 = ops.pack_kmap(f0, F, 2 * tarp, [(0, 0, tar), (tarp, tar, tar)], pf, ('f0', il), split=sp)
         b0 = ops.stack_vec([self.fea_fuse[il][t][0].bias for t in names], ('f0b', il))
         fc = [self.fea_fuse[il][t][1].weight for t in names]
-        Wc = ops.pack_conv3_split(fc, ('f1', il)) if self._decoder_conv_split() else ops.pack_conv3(fc, pf, ('f1', il))
+        Wc = ops.pack_conv3(fc, pf, ('f1', il), split=True if self._decoder_conv_split() else None)
         bc = ops.stack_vec([self.fea_fuse[il][t][1].bias for t in names], ('f1b', il))
         f4 = [self.fea_fuse[il][t][4].weight for t in names]
         # inference (BatchNorm folded into the conv's epilogue): the conv writes GELU(BN(.)) as planes, so fea_fuse[4] runs on the split-plane
         # kernel too (880 -> 490 us per tap at B = 63, profiles/r05_dec_x3_bench_b_edge.log); in training BatchNorm's apply writes fp32
-        W4 = ops.pack_linear_split(f4, ('f4', il)) if self._fuse4_split() else ops.pack_linear(f4, pf, ('f4', il))
+        W4 = ops.pack_linear(f4, pf, ('f4', il), split=self._fuse4_split())
         b4 = ops.stack_vec([self.fea_fuse[il][t][4].bias for t in names], ('f4b', il))
         return Wdec, bdec, W0, b0, Wc, bc, W4, b4
 
@@ -383,14 +381,6 @@ class TaskPrompter(nn.Module):
         return autograd_path.CtrWeightsFn.apply(rawlog, B, T, ('ctrw', il), *[m[0].weight for m in mods], *[m[0].bias for m in mods],
                                                 *[m[2].weight for m in mods], *[m[2].bias for m in mods])
 
-    def _bn_fold(self, bns, conv_biases, tag):
-        return bn_fold(bns, conv_biases, tag)
-
-    def _bn_train(self, y, bns, C, act):
-        """training-mode BatchNorm2d (+act) on [T, rows, ld] pre-activations; updates running stats like nn.BatchNorm2d."""
-        from . import bn as bn_mod
-        return bn_mod.train_forward(y, C, list(bns), act)[0]
-
     def _task_features(self, xsrc, xview, rawlog, rawchan, il, B, acc):
         p, prec = self.p, self.prec
         ps, pf, adt = self._gp('side'), self._gp('fuse'), self.prec.adt
@@ -413,25 +403,13 @@ class TaskPrompter(nn.Module):
         bns = [self.fea_fuse[il][t][2] for t in names]
         if self.training:
             y1 = ops.conv3x3(y0, Wc, F, F, B, h, w, pf, bias=bc, out_dtype=adt)
-            y1 = self._bn_train(y1, bns, F, ACT_GELU)
+            y1 = bn_mod.train_forward(y1, F, list(bns), ACT_GELU)[0]
         else:
-            sc, sh = self._bn_fold(bns, [self.fea_fuse[il][t][1].bias for t in names], ('f2', il))
+            sc, sh = bn_mod.fold(bns, [self.fea_fuse[il][t][1].bias for t in names], ('f2', il))
             y1 = ops.conv3x3(y0, Wc, F, F, B, h, w, pf, bias=sh, colscale=sc, act=ACT_GELU, out_dtype="split" if self._fuse4_split() else adt)
         fea = ops.linear(y1, W4, F, pf, bias=b4, out_dtype=adt)
         wmix = self._ctr_weights(rawlog, il, B, T).detach()
         return ops.ctr_mix(fea, wmix, B, F, acc)
-
-
-def bn_fold(bns, conv_biases, tag):
-    """eval BatchNorm folded into the producing conv's epilogue: scale = g/sqrt(v+eps), shift = b + (cb - m)*scale."""
-    def build():
-        with torch.no_grad():
-            sc = torch.stack([bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps) for bn in bns])
-            cb = torch.stack([b.detach() for b in conv_biases])
-            sh = torch.stack([bn.bias.detach() - bn.running_mean * s for bn, s in zip(bns, sc)]) + cb * sc
-            return sc.contiguous(), sh.contiguous()
-    prm = [q for bn in bns for q in (bn.weight, bn.bias, bn.running_mean, bn.running_var)] + list(conv_biases)
-    return ops._cached((tag, tuple(id(q) for q in prm)), prm, build)
 
 
 def _create_task_prompter(variant, pretrained=False, default_cfg=None, **kwargs):
@@ -516,7 +494,6 @@ def run_heads(kind, heads, fea, B, h4, w4, target, prec, training, lowres=False)
     if torch.is_grad_enabled() and (fea.requires_grad or any(q.requires_grad for hd in heads for q in hd.parameters())):
         from . import autograd_path
         return autograd_path.heads_forward(kind, heads, fea, B, h4, w4, target, prec, training, lowres)
-    from . import bn as bn_mod
     F = heads[0].mt_proj[0].weight.shape[0]
     outs = []
     if kind == 'conv':
@@ -527,7 +504,7 @@ def run_heads(kind, heads, fea, B, h4, w4, target, prec, training, lowres=False)
             if fea.dtype != prec.adt:
                 fea = ops.cast_rows(fea.reshape(-1, fea.shape[-1]), prec.adt).view(fea.shape)
             sp9 = prec.split and ops.split_gemm_ok(ops.pitch(conv_w[0].shape[1]))
-            W9 = ops.pack_upconv9_split(conv_w, 'hc9') if sp9 else ops.pack_upconv9(conv_w, prec, 'hc9')
+            W9 = ops.pack_upconv9(conv_w, prec, 'hc9', split=sp9)
 
             def conv(**epi):
                 return ops.upconv3x3(fea, W9, F, B, h4 // 4, w4 // 4, prec, **epi)
@@ -540,7 +517,7 @@ def run_heads(kind, heads, fea, B, h4, w4, target, prec, training, lowres=False)
             y = conv(bias=ops.stack_vec([hd.mt_proj[0].bias for hd in heads], 'hcb'))
             y = bn_mod.train_forward(y, F, bns, ACT_GELU)[0]
         else:
-            sc, sh = bn_fold(bns, [hd.mt_proj[0].bias for hd in heads], 'hbn')
+            sc, sh = bn_mod.fold(bns, [hd.mt_proj[0].bias for hd in heads], 'hbn')
             y = conv(bias=sh, colscale=sc, act=ACT_GELU)
         for i, hd in enumerate(heads):
             n_out = hd.linear_pred.weight.shape[0]
@@ -567,7 +544,7 @@ def run_heads(kind, heads, fea, B, h4, w4, target, prec, training, lowres=False)
             bn1 = hd.mt_proj[1]
             y = ops.bn_apply(y, F2, bn1.running_mean, torch.rsqrt(bn1.running_var + bn1.eps), bn1.weight.detach(),
                              bn1.bias.detach(), ACT_GELU)
-            sc, sh = bn_fold([hd.mt_proj[4]], [hd.mt_proj[3].bias], 'hd4')
+            sc, sh = bn_mod.fold([hd.mt_proj[4]], [hd.mt_proj[3].bias], 'hd4')
             y = ops.conv3x3(y, Wc, F2, F2, B, 2 * h4, 2 * w4, prec, bias=sh, colscale=sc, act=ACT_GELU)
         n_out = hd.linear_pred.weight.shape[0]
         pred = ops.linear(y[0], ops.pack_linear([hd.linear_pred.weight], prec, 'hp'), n_out, prec,

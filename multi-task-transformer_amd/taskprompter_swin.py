@@ -24,9 +24,10 @@ import math
 import torch
 import torch.nn as nn
 
+from . import bn as bn_mod
 from . import ops
 from ._lib import ACT_GELU, F32, OP_K, OP_R, dtype_code
-from .taskprompter import BatchNorm2d, Mlp, _init_vit_weights, _prec_of, bn_fold, trunc_normal_
+from .taskprompter import BatchNorm2d, Mlp, _init_vit_weights, _prec_of, trunc_normal_
 
 
 # ---- geometry (host side, cached): index tables of the window partition / reverse / merging ----------------------------------------
@@ -272,10 +273,9 @@ class TaskPrompterSwin(nn.Module):
         pass and the product runs on the split-plane LDS-DMA kernel (pre-split weight planes) instead of the register-staged x3 one."""
         N, K = layer.weight.shape[0], layer.weight.shape[1]
         bias = layer.bias.detach()[None] if layer.bias is not None else None
-        if (self.prec.split and torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() and x.shape[1] == K
-                and kw.get("a_rows") is None and x.shape[0] >= self.SPLIT_MIN_ROWS and ops.split_gemm_ok(K)):
-            return ops.linear(ops.split_cast(x), ops.pack_linear_split([layer.weight], tag), N, self.prec, bias=bias, **kw)
-        return ops.linear(x, ops.pack_linear([layer.weight], self.prec, tag), N, self.prec, bias=bias, **kw)
+        split = (self.prec.split and torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() and x.shape[1] == K
+                 and kw.get("a_rows") is None and x.shape[0] >= self.SPLIT_MIN_ROWS and ops.split_gemm_ok(K))
+        return ops.linear(ops.split_cast(x) if split else x, ops.pack_linear([layer.weight], self.prec, tag, split=split), N, self.prec, bias=bias, **kw)
 
     def _forward_nograd(self, img):
         p, prec = self.p, self.prec
@@ -441,7 +441,7 @@ class TaskPrompterSwin(nn.Module):
         for t in names:
             dec_w += [self.fea_decode_spa[il][t][0].weight, self.fea_decode_chan[il][t][0].weight]
             dec_b += [self.fea_decode_spa[il][t][0].bias, self.fea_decode_chan[il][t][0].bias]
-        Wdec = ops.pack_linear_split(dec_w, ('swdec', il)) if sp else ops.pack_linear(dec_w, prec, ('swdec', il))
+        Wdec = ops.pack_linear(dec_w, prec, ('swdec', il), split=sp)
         bdec = ops.stack_vec(dec_b, ('swdecb', il))
         cat = ops.Split.empty((T, B * hw, 2 * tarp), xsrc.device) if sp else torch.empty(T, B * hw, 2 * tarp, dtype=prec.adt, device=xsrc.device)
         ops.linear(mod, Wdec, tar, prec, bias=bdec, out=cat, batch_inner=2, d_z=(B * hw * 2 * tarp, tarp), ldd=2 * tarp, n_store=tarp)
@@ -457,7 +457,7 @@ class TaskPrompterSwin(nn.Module):
                     buf[i, :, tarp:tarp + tar] = w2[:, tar:]
                 return buf.to(prec.adt)
         if sp:
-            W0 = ops.pack_kmap_split(f0, F, 2 * tarp, [(0, 0, tar), (tarp, tar, tar)], ('swf0', il))
+            W0 = ops.pack_kmap(f0, F, 2 * tarp, [(0, 0, tar), (tarp, tar, tar)], prec, ('swf0', il), split=True)
         else:
             W0 = ops._cached(('swf0', il, prec.name, tuple(id(q) for q in f0)), f0, build_f0)
         b0 = ops.stack_vec([self.fea_fuse[il][t][0].bias for t in names], ('swf0b', il))
@@ -468,11 +468,10 @@ class TaskPrompterSwin(nn.Module):
         Wc = ops.pack_conv3([m[1].weight for m in ff], prec, ('swf1', il))
         bns = [m[2] for m in ff]
         if self.training:
-            from . import bn as bn_mod
             y1 = ops.conv3x3(y0, Wc, F, F, B, 2 * h, 2 * w, prec, bias=ops.stack_vec([m[1].bias for m in ff], ('swf1b', il)))
             y1 = bn_mod.train_forward(y1, F, list(bns), ACT_GELU)[0]
         else:
-            sc, sh = bn_fold(bns, [m[1].bias for m in ff], ('swf2', il))
+            sc, sh = bn_mod.fold(bns, [m[1].bias for m in ff], ('swf2', il))
             y1 = ops.conv3x3(y0, Wc, F, F, B, 2 * h, 2 * w, prec, bias=sh, colscale=sc, act=ACT_GELU)
         W4 = ops.pack_conv3([m[4].weight for m in ff], prec, ('swf4', il))
         return ops.conv3x3(y1, W4, F, F, B, 2 * h, 2 * w, prec, bias=ops.stack_vec([m[4].bias for m in ff], ('swf4b', il)))

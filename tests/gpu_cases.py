@@ -451,7 +451,7 @@ def gemm_cases():
                   d_zo=rows * Cop, conv=dict(H=H, W=W, C=Ci, Cp=Cp, dil=dil, flip=flip), alpha=1.0, n_store=Cop, colshift=rnd(g, Zc, Co), col_zo=Co)
         cases.append((f"conv3_split_{Bc}x{H}x{W}_c{Ci}_dil{dil}_flip{flip}", "gemm", kw, TOL_X3))
         cases.append((f"conv3_split_bnfold_gelu_{Bc}x{H}x{W}_c{Ci}", "gemm", dict(kw, D=torch.full((Zc, rows, Cop), 7.0), colscale=rnd(g, Zc, Co), act=1), TOL_X3))
-    # 1e+a. the prediction dgrad of TaskHeadsFn on the 128-row LDS-DMA kernel (forced variant 4): K = pad8(n) = 8 / 24 — less than one 64-deep K
+    # 1e+a. the prediction dgrad of TaskHeadsFn on the 128-row LDS-DMA kernel (forced variant 4): K = pitch(n) = 8 / 24 — less than one 64-deep K
     #       step, chunks past K read the zero page — a tall M, N = 352 / 176, bf16 output with n_store = pitch
     for (M, N, K) in ((5000, 352, 24), (3001, 176, 8)):
         kw = dict(A=rnd(g, M, K, dtype=torch.bfloat16), B=rnd(g, N, K, dtype=torch.bfloat16), D=torch.full((M, N), 7.0, dtype=torch.bfloat16), M=M, N=N, K=K,

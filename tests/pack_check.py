@@ -2,13 +2,11 @@
 tests/test_host_cpu.py and on the HIP kernel by tests/test_gpu_ops.py.  Casts are round-to-nearest-even on both sides: bit-exact."""
 import torch
 
-import mtt_amd
 from mtt_amd import ops
 
 
-def pad8(n):
-    import mtt_amd
-    return mtt_amd.ops.pad8(n)              # the product's channel-pitch rule (multiples of 8; of 32 from ops.PITCH32_FROM channels on)
+def pitch(n):
+    return ops.pitch(n)                     # the product's channel-pitch rule (multiples of 8; of 32 from ops.PITCH32_FROM channels on)
 
 
 def _params(device, shapes, seed=0):
@@ -18,7 +16,7 @@ def _params(device, shapes, seed=0):
 
 def _ref_linear(ws, dtype):
     N, K = ws[0].shape[0], ws[0].numel() // ws[0].shape[0]
-    buf = torch.zeros(len(ws), N, pad8(K), dtype=torch.float32, device=ws[0].device)
+    buf = torch.zeros(len(ws), N, pitch(K), dtype=torch.float32, device=ws[0].device)
     for z, w in enumerate(ws):
         buf[z, :, :K] = w.detach().reshape(N, K)
     return buf.to(dtype)
@@ -30,9 +28,9 @@ def _ref_conv3(ws, dtype, transpose):
         w = w.detach()
         w = w.permute(1, 2, 3, 0) if transpose else w.permute(0, 2, 3, 1)
         R, _, _, Cin = w.shape
-        buf = torch.zeros(R, 9, pad8(Cin), dtype=torch.float32, device=w.device)
+        buf = torch.zeros(R, 9, pitch(Cin), dtype=torch.float32, device=w.device)
         buf[:, :, :Cin] = w.reshape(R, 9, Cin)
-        out.append(buf.reshape(R, 9 * pad8(Cin)))
+        out.append(buf.reshape(R, 9 * pitch(Cin)))
     return torch.stack(out).to(dtype)
 
 
@@ -40,9 +38,9 @@ def _ref_up9(ws, dtype):
     out = []
     for w in ws:
         Co, Ci = w.shape[:2]
-        buf = torch.zeros(9, pad8(Co), pad8(Ci), dtype=torch.float32, device=w.device)
+        buf = torch.zeros(9, pitch(Co), pitch(Ci), dtype=torch.float32, device=w.device)
         buf[:, :Co, :Ci] = w.detach().permute(2, 3, 0, 1).reshape(9, Co, Ci)
-        out.append(buf.reshape(9 * pad8(Co), pad8(Ci)))
+        out.append(buf.reshape(9 * pitch(Co), pitch(Ci)))
     return torch.stack(out).to(dtype)
 
 
@@ -67,11 +65,9 @@ def check_packs(device):
         for prec in (bf, x3):
             got = ops.pack_linear(ws, prec, ('t', len(shapes), shapes[0]))
             same(got, _ref_linear(ws, prec.adt))
-        sp = ops.pack_linear_split(ws, ('ts', shapes[0]))
-        ref = _ref_linear(ws, torch.float32)
-        hi = ref.to(torch.bfloat16)
-        same(sp.hi, hi)
-        same(sp.lo, (ref - hi.float()).to(torch.bfloat16))
+        sp = ops.pack_linear(ws, x3, ('ts', shapes[0]), split=True)      # fp32 storage too: planes never take the parameter-is-the-operand shortcut
+        assert isinstance(sp, ops.Split)
+        same_split(sp, _ref_linear(ws, torch.float32))
     # conv layouts
     ws = _params(device, [(52, 44, 3, 3)] * 3, 1)
     for prec in (bf, x3):
@@ -79,8 +75,11 @@ def check_packs(device):
         same(ops.pack_conv3(ws, prec, 'c', transpose=True), _ref_conv3(ws, prec.adt, True))
         same(ops.pack_upconv9(ws, prec, 'u'), _ref_up9(ws, prec.adt))
     # the same layouts as pre-split planes (x3f: the split-plane implicit-GEMM conv and the nine-tap head GEMM)
-    same_split(ops.pack_conv3_split(ws, 'cs'), _ref_conv3(ws, torch.float32, False))
-    same_split(ops.pack_upconv9_split(ws, 'us'), _ref_up9(ws, torch.float32))
+    same_split(ops.pack_conv3(ws, bf, 'cs', split=True), _ref_conv3(ws, torch.float32, False))
+    same_split(ops.pack_upconv9(ws, bf, 'us', split=True), _ref_up9(ws, torch.float32))
+    for prec in (bf, x3):                                          # planes and the one-tensor pack of one tag are distinct entries
+        same(ops.pack_conv3(ws, prec, 'cs', split=False), _ref_conv3(ws, prec.adt, False))
+        same(ops.pack_upconv9(ws, prec, 'us'), _ref_up9(ws, prec.adt))
     w32 = _params(device, [(24, 64, 3, 3)] * 2, 8)                # channel pitch % 32 == 0: pack_conv3 itself picks the split layout under x3f
     got = ops.pack_conv3(w32, ops.Prec("x3f"), 'c32')
     assert isinstance(got, ops.Split)
@@ -95,7 +94,8 @@ def check_packs(device):
         ref[z, :, :44] = w2[:, :44]
         ref[z, :, 48:92] = w2[:, 44:]
     same(got, ref.to(torch.bfloat16))
-    same_split(ops.pack_kmap_split(ws, 52, 96, [(0, 0, 44), (48, 44, 44)], 'ks'), ref)
+    same_split(ops.pack_kmap(ws, 52, 96, [(0, 0, 44), (48, 44, 44)], bf, 'k', split=True), ref)             # same tag as the bf16 pack above: another entry
+    same(ops.pack_kmap(ws, 52, 96, [(0, 0, 44), (48, 44, 44)], bf, 'k'), ref.to(torch.bfloat16))
     bs = _params(device, [(301,)] * 4, 3)
     same(ops.stack_vec(bs, 'b'), torch.stack([b.detach() for b in bs]))
     # transposed packs: tiles with ragged edges, several tiles per chunk, and the small-matrix fallback
@@ -103,6 +103,57 @@ def check_packs(device):
         w, = _params(device, [shape], 4)
         same(ops.pack_linear_T(w, torch.bfloat16, ('T', shape)), w.detach().t().contiguous().to(torch.bfloat16))
         same(ops.pack_linear_T(w, torch.float32, ('T32', shape)), w.detach().t().contiguous())
+
+
+def check_pitch_key(device):
+    """The pitch rule (ops.PITCH32_FROM) is part of every pack key: after the global is assigned, with nothing cleared, the packs follow
+    the new rule, and the entries of the old rule are served again (the same objects) once it is back."""
+    from mtt_amd import bn
+    saved = ops.PITCH32_FROM
+    bf = ops.Prec("bf16")
+    wl = _params(device, [(12, 44)], 11)
+    c20 = _params(device, [(12, 20, 3, 3)], 12)
+    c44 = _params(device, [(12, 44, 3, 3)], 13)
+    g = torch.Generator().manual_seed(14)
+    bns = [torch.nn.BatchNorm2d(12).to(device).eval() for _ in range(2)]
+    for m in bns:
+        for t in (m.weight.data, m.bias.data, m.running_mean):
+            t.copy_(torch.randn(12, generator=g))
+        m.running_var.copy_(torch.rand(12, generator=g) + 0.5)
+    fold_sc = torch.stack([m.weight.detach() * torch.rsqrt(m.running_var + m.eps) for m in bns])
+    fold_sh = torch.stack([m.bias.detach() - m.running_mean * s for m, s in zip(bns, fold_sc)])
+
+    def packs(K44, C20, C44):
+        """every pack as one tensor and as planes, shapes and contents checked against the rule in force"""
+        assert (pitch(44), pitch(20)) == (K44, C20)
+        out = []
+        for split in (False, True):
+            got = [ops.pack_linear(wl, bf, 'pk', split=split), ops.pack_conv3(c20, bf, 'pk20', split=split),
+                   ops.pack_conv3(c44, bf, 'pk44', split=split)]
+            assert [tuple(t.shape) for t in got] == [(1, 12, K44), (1, 12, 9 * C20), (1, 12, 9 * C44)]
+            refs = [_ref_linear(wl, torch.float32), _ref_conv3(c20, torch.float32, False), _ref_conv3(c44, torch.float32, False)]
+            for t, r in zip(got, refs):
+                assert isinstance(t, ops.Split) == split
+                same_split(t, r) if split else same(t, r.to(torch.bfloat16))
+            out += got
+        f = bn.fold(bns, None, 'pkbn')                    # a _cached user: independent of the pitch, still right and still cached
+        same(f[0], fold_sc)
+        same(f[1], fold_sh)
+        assert bn.fold(bns, None, 'pkbn') is f
+        return out + [f]
+
+    try:
+        ops.PITCH32_FROM = 160                            # the default rule, also in the suite's wide-pitch run
+        old = packs(48, 24, 48)
+        ops.PITCH32_FROM = 33                             # assigned as bench.py / conftest.py / train_check do: nothing cleared
+        new = packs(64, 24, 64)
+        assert all(a is not b for a, b in zip(old, new))
+        ops.PITCH32_FROM = 160
+        assert all(a is b for a, b in zip(old, packs(48, 24, 48)))
+        ops.PITCH32_FROM = 33
+        assert all(a is b for a, b in zip(new, packs(64, 24, 64)))
+    finally:
+        ops.PITCH32_FROM = saved
 
 
 def check_refresh(device):

@@ -266,7 +266,7 @@ def test_dma_gemm_and_conv_kernels_agree_with_x3_at_bench_shapes():
         # the same kernel on MTT_SPLIT planes (K-concatenated x3 product) with fp32 operands that are NOT bf16-representable
         xf = torch.randn(M, K, device="cuda", generator=g)
         wp = torch.nn.Parameter(torch.randn(N, K, device="cuda", generator=g) / K ** 0.5)
-        ws = ops.pack_linear_split([wp], ("t_split", tag))
+        ws = ops.pack_linear([wp], x3, ("t_split", tag), split=True)
         assert mtt_amd._lib.gemm_variant(A=x, B=w, D=x, A_lo=x, B_lo=w, M=M, N=N, K=K, a_dtype=2, b_dtype=2, d_dtype=0, prec=1, lda=K, ldb=K, ldd=N,
                                          batch=1) == 8
         ys = ops.linear(ops.split_cast(xf), ws, N, x3, bias=b, out_dtype=torch.float32)
@@ -275,7 +275,7 @@ def test_dma_gemm_and_conv_kernels_agree_with_x3_at_bench_shapes():
         pu.report("kernel_parity", kernel="gemm_dma_split", shape=tag, M=M, N=N, K=K, rel=e)
         assert e < 3e-5, (tag, e)
     B, H, W, F = 4, 128, 128, 350
-    Fp = ops.pad8(F)
+    Fp = ops.pitch(F)
     xin = torch.zeros(2, B * H * W, Fp, device="cuda")
     xin[..., :F] = torch.randn(2, B * H * W, F, device="cuda", generator=g)
     xin = xin.bfloat16()

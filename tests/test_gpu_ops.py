@@ -40,5 +40,6 @@ def test_segcopy_packs_refresh_and_gradient_scatter_on_device():
         pytest.skip("no GPU")
     import pack_check
     pack_check.check_packs("cuda")
+    pack_check.check_pitch_key("cuda")
     pack_check.check_refresh("cuda")
     pack_check.check_unpack("cuda")

@@ -137,7 +137,7 @@ def test_x3f_mode_forward_x3_on_split_planes_backward_bf16(emulated, monkeypatch
     # qkv, proj, fc1, fc2 per block + per tap fea_decode (on the planes `modulate` writes) and fea_fuse[0] (on the planes its epilogue writes)
     n_split = sum(1 for n, adt, pr, _ in seen if n == "gemm" and adt == 2 and pr == 1)
     # (with the multiple-of-32 pitch on the miniature's 52-channel maps — MTT_TEST_PITCH32_FROM — the decoder's convs and head GEMM join them)
-    assert n_split == 4 * n_blocks + 2 * n_taps if mtt_amd.ops.pad8(52) == 56 else n_split > 4 * n_blocks + 2 * n_taps
+    assert n_split == 4 * n_blocks + 2 * n_taps if mtt_amd.ops.pitch(52) == 56 else n_split > 4 * n_blocks + 2 * n_taps
     assert sum(1 for n, _, _, _ in seen if n == "modulate") == n_taps
     assert sum(1 for n, _, pr, dt in seen if n == "attn_fwd" and dt == 2 and pr == 1) == n_blocks
     assert sum(1 for n, *_ in seen if n == "attn_bwd") == n_blocks
@@ -195,7 +195,7 @@ def test_split_plane_conv_chunks_the_batch_at_the_kernels_row_limit(emulated, mo
     ref = torch.nn.functional.conv2d(x[0].view(B, H, W, Ci).permute(0, 3, 1, 2), ws[0].detach(), bias[0], padding=1).permute(0, 2, 3, 1)
     assert float((whole[0].view(B, H, W, -1)[..., :Co] - ref).norm() / ref.norm()) < 1e-4
     assert ops.split_conv_ok(352, 352) and not ops.split_conv_ok(20) and not ops.split_conv_ok(8192, 64) and not ops.split_conv_ok(4096, 60000)
-    assert ops.split_conv_ok(300) == (ops.pad8(300) == 320)        # the multiple-of-32 channel pitch from ops.PITCH32_FROM channels on
+    assert ops.split_conv_ok(300) == (ops.pitch(300) == 320)        # the multiple-of-32 channel pitch from ops.PITCH32_FROM channels on
     ops.clear_pack_cache()
 
 
@@ -865,6 +865,7 @@ def test_persistent_packs_match_torch_relayouts_on_emulator(emulated):
     """ops.seg_pack / mtt_segcopy (emulated): every pack layout bit-exact against a plain torch re-layout; one refresh per parameter update."""
     import pack_check
     pack_check.check_packs("cpu")
+    pack_check.check_pitch_key("cpu")
     pack_check.check_refresh("cpu")
     pack_check.check_unpack("cpu")
 
@@ -926,7 +927,7 @@ def test_gemm_policy_routes_the_round5_kernels():
     assert conv(63 * 1024, 350, 352, variant=1) == 0           # MTT_GEMM_GENERAL
     assert conv(1024, 40, 32, variant=3) == 12                 # forced (the op tests' small shapes)
     assert conv(63 * 1024, 350, 352, a_dtype=2, b_dtype=2, prec=1, A_lo=torch.zeros(1), B_lo=torch.zeros(1), d_dtype=0) == 9
-    # the prediction dgrad of TaskHeadsFn: K = pad8(n) on the 128-row LDS-DMA kernel when forced, the general kernel otherwise
+    # the prediction dgrad of TaskHeadsFn: K = pitch(n) on the 128-row LDS-DMA kernel when forced, the general kernel otherwise
     head = dict(M=63 * 16384, N=352, K=24, a_op=0, b_op=0, a_dtype=1, b_dtype=1, d_dtype=1, prec=0, lda=24, ldb=24, ldd=352, batch=1)
     assert gv(**head, variant=4) == 4 and gv(**head) in (0, 4)
 

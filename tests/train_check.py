@@ -95,7 +95,7 @@ def skip_unless_own_pitch(cfg):
     import mtt_amd
     E = cfg["embed_dim"] + cfg["pred_const"]
     dims = (cfg["embed_dim"], E, E // 2, E // 4)
-    if any(d != mtt_amd.ops.pad8(d) for d in dims):
+    if any(d != mtt_amd.ops.pitch(d) for d in dims):
         pytest.skip(f"InvPT training path: widths {dims} are not their own channel pitch under PITCH32_FROM = {mtt_amd.ops.PITCH32_FROM}")
 
 

@@ -16,7 +16,7 @@ ops.call = lambda name, **kw: _call(name, **(dict(kw, variant=FORCE["v"]) if nam
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 Z, C = 6, 350
 prec = ops.Prec("bf16")
-Cp = ops.pad8(C)
+Cp = ops.pitch(C)
 ws = [torch.randn(C, C, 3, 3, device="cuda") * 0.02 for _ in range(Z)]
 wp = ops.pack_conv3(ws, prec, "bench")
 wd = ops.pack_conv3(ws, prec, "bench", transpose=True)

@@ -35,13 +35,13 @@ def timed(fn, rounds=5, inner=4):
     return statistics.median(ts)
 
 
-# (name, Z, N, K) : D[z] [M, pad8(N)] = A[z] [M, pad8(K)] @ W[z] [N, pad8(K)]^T + bias
+# (name, Z, N, K) : D[z] [M, pitch(N)] = A[z] [M, pitch(K)] @ W[z] [N, pitch(K)]^T + bias
 for name, Z, N, K in (("fea_decode fwd (12 = 6 tasks x spa/chan)", 12, 300, 1024), ("fea_fuse[0] fwd", 6, 350, 608), ("fea_fuse[4] fwd", 6, 350, 350),
                       ("fea_decode dgrad", 12, 1024, 300), ("fea_fuse[0] dgrad", 6, 608, 350), ("fea_fuse[4] dgrad", 6, 350, 350),
                       ("head linear_pred (128 x 128 map, 21 classes)", 1, 21, 350), ("encoder qkv (for reference)", 1, 3072, 1024),
                       ("channel attention, prompt rows (M = 378)", 1, 1024, 1024)):
     M = M_OF.get(name, 63 * 1024)
-    Np, Kp = ops.pad8(N), ops.pad8(K)
+    Np, Kp = ops.pitch(N), ops.pitch(K)
     A = (torch.rand(Z, M, Kp, device="cuda") - 0.5).bfloat16()
     A[..., K:] = 0
     W = (torch.rand(Z, N, Kp, device="cuda") - 0.5).bfloat16()

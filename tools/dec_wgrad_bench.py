@@ -51,7 +51,7 @@ def run(dy, x, N, Kp, Z, S, lda, ldb, a_zo, b_zo, variant):
 
 for name, N, K, Z, pair in (("fea_decode (one half of the pair)", 300, 1024, 6, True), ("fea_fuse[0]", 350, 608, 6, False),
                             ("fea_fuse[4]", 350, 352, 6, False)):
-    Np, Kp = ops.pad8(N), ops.pad8(K)
+    Np, Kp = ops.pitch(N), ops.pitch(K)
     lda = 2 * Np if pair else Np
     dy = (torch.rand(Z, M, lda, device="cuda") - 0.5).bfloat16()
     x = (torch.rand((2 * Z if pair else Z), M, Kp, device="cuda") - 0.5).bfloat16()

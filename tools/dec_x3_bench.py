@@ -37,12 +37,12 @@ def timed(fn, rounds=3):
 
 
 for name, Z, N, K, pair in (("fea_decode", 12, 300, 1024, True), ("fea_fuse0", 6, 350, 608, False), ("fea_fuse4", 6, 350, 352, False)):
-    Np = ops.pad8(N)
+    Np = ops.pitch(N)
     x = torch.randn(Z, M, K, device="cuda")
     ws = [torch.nn.Parameter(torch.randn(N, K, device="cuda") * 0.05) for _ in range(Z)]
     b = torch.randn(Z, N, device="cuda")
     w32 = ops.pack_linear(ws, x3, ("b32", name))
-    wsp = ops.pack_linear_split(ws, ("bsp", name))
+    wsp = ops.pack_linear(ws, x3f, ("bsp", name), split=True)
     kw = dict(batch_inner=2, d_z=(M * 2 * Np, Np), ldd=2 * Np, n_store=Np) if pair else {}
     shape = (Z // 2, M, 2 * Np) if pair else (Z, M, Np)
     o32 = torch.empty(shape, device="cuda")
@@ -60,12 +60,12 @@ for name, Z, N, K, pair in (("fea_decode", 12, 300, 1024, True), ("fea_fuse0", 6
 
 # the fea_fuse 3x3 conv (6 x [63 * 32 * 32, 352] -> 350, K = 9 * 352) and the nine-tap head GEMM (N = 9 * 352) on planes
 Z, Ci, Co, B, H, W = 6, 350, 350, 63, 32, 32
-Cp = ops.pad8(Ci)
+Cp = ops.pitch(Ci)
 xs = ops.Split.empty((Z, B * H * W, Cp), "cuda")
 xs.hi.normal_(); xs.lo.normal_(std=1e-3)
 ws = [torch.nn.Parameter(torch.randn(Co, Ci, 3, 3, device="cuda") * 0.05) for _ in range(Z)]
-wc = ops.pack_conv3_split(ws, "bconv")
+wc = ops.pack_conv3(ws, x3f, "bconv", split=True)
 t_conv = timed(lambda: ops.conv3x3(xs, wc, Co, Ci, B, H, W, x3f, out_dtype=torch.float32))
-w9 = ops.pack_upconv9_split(ws, "b9")
+w9 = ops.pack_upconv9(ws, x3f, "b9", split=True)
 t_nine = timed(lambda: ops.linear(xs, w9, w9.shape[1], x3f, out_dtype=torch.float32))
 print(f"conv3x3 on planes (N = 350, K = 3168, z = 6): {t_conv:7.1f} us | nine-tap head GEMM (N = {w9.shape[1]}, K = 352, z = 6): {t_nine:7.1f} us", flush=True)

@@ -59,7 +59,7 @@ for name, M, N, K, act in SHAPES:
     x = (torch.rand(M, K, device="cuda") * 2 - 1).bfloat16()
     w = (torch.rand(1, N, K, device="cuda") * 2 - 1).bfloat16()
     b = torch.randn(1, N, device="cuda")
-    out = torch.empty(1, M, ops.pad8(N), device="cuda", dtype=torch.bfloat16)
+    out = torch.empty(1, M, ops.pitch(N), device="cuda", dtype=torch.bfloat16)
     XT = torch.zeros(M, N, device="cuda") if act == 2 else None
     RS = torch.ones(M // 1030 + 1, 2, device="cuda") if act == 2 else None
     AUX = torch.randn(1, M, N, device="cuda").bfloat16() if act == 3 else None
@@ -70,7 +70,7 @@ for name, M, N, K, act in SHAPES:
         x3 = ops.Prec("x3f")
         xs = ops.split_cast((torch.rand(M, K, device="cuda") * 2 - 1))
         wp = torch.nn.Parameter(torch.rand(N, K, device="cuda") * 2 - 1)
-        ws = ops.pack_linear_split([wp], ("bench", name))
+        ws = ops.pack_linear([wp], x3, ("bench", name), split=True)
         o32 = torch.empty(1, M, N, device="cuda")
         m2, b2 = timed(lambda: ops.linear(xs, ws, N, x3, bias=b, out=o32), a.rounds)
         line += f"  |  split x3: {2.0 * M * N * K / m2 / 1e9:6.0f} TF/s effective = {6.0 * M * N * K / m2 / 1e9:6.0f} MFMA TF/s ({m2 * 1e3:7.1f} us)"
@@ -104,7 +104,7 @@ x3 = ops.Prec("x3f")
 for (M, N, K) in ((M63, 1024, 1024), (5000, 768, 4096), (777, 512, 64), (3000, 1280, 128), (2049, 512, 192)):
     xs = ops.split_cast((torch.rand(M, K, device="cuda") * 2 - 1))
     wp = torch.nn.Parameter(torch.rand(N, K, device="cuda") * 2 - 1)
-    ws = ops.pack_linear_split([wp], ("chk", M, N, K))
+    ws = ops.pack_linear([wp], x3, ("chk", M, N, K), split=True)
     b = torch.randn(1, N, device="cuda")
     ref = (xs.hi.double() + xs.lo.double()) @ (ws.hi[0].double() + ws.lo[0].double()).t() + b.double()
     first, bad = None, 0

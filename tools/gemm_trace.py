@@ -31,7 +31,7 @@ for name, M, N, K, act in SHAPES:
     x = (torch.rand(M, K, device="cuda") * 2 - 1).bfloat16()
     w = (torch.rand(1, N, K, device="cuda") * 2 - 1).bfloat16()
     b = torch.randn(1, N, device="cuda")
-    out = torch.empty(1, M, ops.pad8(N), device="cuda", dtype=torch.bfloat16)
+    out = torch.empty(1, M, ops.pitch(N), device="cuda", dtype=torch.bfloat16)
     XT = torch.zeros(M, N, device="cuda") if act == 2 else None
     RS = torch.ones(M // 1030 + 1, 2, device="cuda") if act == 2 else None
 

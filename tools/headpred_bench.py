@@ -33,7 +33,7 @@ a = torch.randn(M, K, device="cuda")
 for N in (21, 7, 1):
     w = torch.randn(N, K, device="cuda") * 0.1
     b = torch.randn(N, device="cuda")
-    Np = ops.pad8(N)
+    Np = ops.pitch(N)
     kw = dict(A=a, B=w, M=M, N=N, K=K, a_op=0, b_op=0, a_dtype=0, b_dtype=0, d_dtype=0, prec=1, lda=K, ldb=K, ldd=Np, batch=1, batch_inner=1, alpha=1.0,
               colshift=b, n_store=Np)
     o1, o2 = torch.empty(M, Np, device="cuda"), torch.empty(M, Np, device="cuda")

@@ -16,7 +16,7 @@ from mtt_amd import ops  # noqa: E402
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 63
 Z, C, h, w = 6, 350, 32, 32
 prec = ops.Prec("bf16")
-Cp = ops.pad8(C)
+Cp = ops.pitch(C)
 torch.manual_seed(0)
 ws = [torch.nn.Parameter(torch.randn(C, C, 3, 3, device="cuda") * 0.02) for _ in range(Z)]
 bs = [torch.nn.Parameter(torch.randn(C, device="cuda") * 0.1) for _ in range(Z)]
