@@ -1,11 +1,15 @@
-"""Training path of TaskPrompter: the same HIP kernels wrapped as torch.autograd.Functions with
+"""TaskPrompter's forward and its training path: the HIP kernels wrapped as torch.autograd.Functions with
 hand-written backward passes (dgrad / wgrad are the same MFMA GEMM kernel with transposed operand
 views: MTT_OP_R; conv dgrad = the implicit-GEMM conv with mirrored taps; conv wgrad = MTT_OP_CONV_R).
 
-The forward schedule is identical to TaskPrompter._forward_nograd; autograd only carries the fp32
-residual stream, the logit side channels and the decoder feature maps between Functions.  Round 1
-attention backward materialises P per (batch, head) with the batched GEMM + row-softmax kernels
-(no N x N tensor ever leaves the backward), see DESIGN.md.
+The encoder has ONE forward (backbone_forward): the launches of a block live in attn_half / mlp_half, which the
+autograd nodes AttnHalfFn / MlpHalfFn call with keep=True and a forward that nobody differentiates calls with
+keep=False (no statistics, log-sum-exp or GELU' side output is written then); InvPT's ViT (invpt_autograd.vit_taps)
+runs on the same two bodies.  The front of cal_task_feature is shared the same way (_task_features); its tail and the
+heads keep a fused inference schedule of their own (TaskPrompter._fuse_tail, taskprompter.run_heads).  With a
+backward, autograd carries only the fp32 residual stream, the logit side channels and the decoder feature maps
+between Functions.  Round 1 attention backward materialises P per (batch, head) with the batched GEMM + row-softmax
+kernels (no N x N tensor ever leaves the backward), see DESIGN.md.
 """
 import math
 
@@ -240,6 +244,13 @@ def _dgrad(dy, wpack2d, M, N_in, K_out, prec, out_dtype, **epi):
 
 
 # =================================================================================================
+def layernorm(x, gamma, beta, eps, prec, out_dtype, keep):
+    """LayerNorm as an autograd node (keep) or as its launch alone, without the statistics only a backward reads"""
+    if keep:
+        return LayerNormFn.apply(x, gamma, beta, eps, prec, out_dtype)
+    return ops.layernorm(x, gamma, beta, eps, prec, out_dtype=out_dtype)[0]
+
+
 class LayerNormFn(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, prec, out_dtype):
@@ -309,6 +320,84 @@ def _ln_bwd_join(dres, x, dy, gamma, mean, rstd, eps):
     return out, dg, db
 
 
+def attn_half(XT, g1, b1, eps, Wqkv, bqkv, Wproj, bproj, Wtt, btt, Wtt1, btt1, rowscale, geo, prec, tag, *, keep, gp=None):
+    """The launches of a block's first half (AttnHalfFn) -> ((XT2, rawlog | None, rawchan | None), tensors for the backward | None).
+    THE one statement of this half: AttnHalfFn.forward calls it with keep=True and saves; a forward nobody differentiates calls it with
+    keep=False.  `keep` decides what the backward needs and nothing else: LayerNorm's statistics, the attention's log-sum-exp, the
+    row-group form of the proj GEMM's output mapping (also taken whenever a DropPath `rowscale` rides on it), the saved tuple.
+    gp = the (enc, attn, side) operand precisions of an error-attribution run (taskprompter._group_precs: fp32 storage, inference only)."""
+    B, N, nH, T, h, w, nwin = geo[:7]
+    side = geo[7] if len(geo) > 7 else True              # False: no consumer of this block's channel logits (not a tap): skip that pass
+    pe, pa, ps = gp or (prec, prec, prec)
+    assert not keep or pe.name == pa.name == ps.name == prec.name, "per-group precisions are inference-only"
+    C, hw = nH * 64, h * w
+    chan = Wtt is not None
+    split = prec.split                       # x3f: x3 products on pre-split planes (LDS-DMA kernel), bf16 backward on the hi planes
+    odt = "split" if split else prec.adt     # storage dtype (a group override only changes operand rounding)
+    xn, mean, rstd = ops.layernorm(XT, g1, b1, eps, prec, save_stats=keep, out_dtype=odt)
+    wq = ops.pack_linear([Wqkv], pe, tag + ('qkv',), split=split)
+    wp = ops.pack_linear([Wproj], pe, tag + ('proj',), split=split)
+    qkv = ops.linear(xn, wq, 3 * C, pe, bias=bqkv[None], out_dtype=odt)[0]
+    flash = keep and (split or (FLASH_BWD and prec.name == "bf16" and qkv.dtype == torch.bfloat16))
+    if not split and pa.adt != qkv.dtype:                        # attribution: bf16 attention inside an fp32-storage run
+        q16 = ops.cast2d(qkv, qkv.shape[0], 3 * C, 3 * C, pa.adt, ldd=3 * C)
+        ao16, rawlog, lse = ops.attention(q16, B, N, nH, T, pa)
+        ao = ops.cast2d(ao16, ao16.shape[0], C, C, prec.adt, ldd=C)
+    else:
+        ao, rawlog, lse = ops.attention(qkv, B, N, nH, T, pa, want_lse=flash)
+    XT2 = torch.empty_like(XT)
+    rows = dict(d_rows=(N, N * C, C), M=B * N) if keep or rowscale is not None else {}
+    ops.linear(ao, wp, C, pe, bias=bproj[None], out=XT2, resid=XT, rowscale=rowscale, n_prompt=T, **rows)
+    cq = wt = wt1 = xp32 = rawchan = None
+    if chan:                                 # channel attention: queries token_trans(norm1(prompts)), keys norm1(x)^T, windowed (:216-250)
+        wt = ops.pack_linear([Wtt], ps, tag + ('tt',))
+        wt1 = ops.pack_linear([Wtt1], ps, tag + ('tt1',))
+        if split:
+            # its patch rows are read as the planes LayerNorm wrote (no fp32 copy of the normalised tokens), its T prompt rows per image are
+            # gathered into a small fp32 matrix
+            xp32 = ops.prompt_rows32(xn, B, N, T, C)
+            cq = ops.linear(xp32, wt, hw, ps, bias=btt[None], M=B * T)[0]
+        else:
+            cq = ops.linear(xn, wt, hw, ps, bias=btt[None], a_rows=(T, N * C, C), M=B * T)[0]
+        if side:
+            xnc = xn if split or ps.adt == xn.dtype else ops.cast2d(xn, xn.shape[0], C, C, ps.adt, ldd=C)
+            rawchan = ops.chan_logits(cq, xnc, B, T, N, C, (h, w), (nwin, nwin))
+        pr = XT2.view(B, N, C)[:, :T]
+        ops.linear(cq, wt1, C, ps, bias=btt1[None], out=pr, d_rows=(T, N * C, C), resid=pr, rowscale=rowscale, n_prompt=T, M=B * T)
+    # the backward's operands: the bf16 hi planes in the x3f mode (its backward IS bf16; the channel attention's reads them too)
+    saved = (XT, g1, mean, rstd, ops._hi(xn), ops._hi(qkv), ops._hi(ao), ops._hi(wq), ops._hi(wp), rowscale, lse, cq, wt, wt1, xp32) if keep else None
+    return (XT2, rawlog, rawchan), saved
+
+
+def mlp_half(XT2, g2, b2n, eps, W1, b1, W2, b2, rowscale, geo, prec, tag, *, keep, pe=None):
+    """The launches of a block's second half (MlpHalfFn) -> (XT3, tensors for the backward | None); one statement, as attn_half:
+    `keep` adds LayerNorm's statistics, fc1's auxiliary output and the row-group form of fc2's output mapping.  pe = the 'enc' operand
+    precision of an error-attribution run."""
+    B, N, T = geo
+    pe = pe or prec
+    assert not keep or pe.name == prec.name
+    C, Hd = W1.shape[1], W1.shape[0]
+    # the split-plane kernel: whole 32-deep K steps (InvPT's 288-channel stage included; else register-staged x3).  MLP_SPLIT_RULE64: the rule of
+    # rounds 3-5 (multiples of 64), for A/B runs
+    split = prec.split and ((C % 64 == 0 and Hd % 64 == 0) if MLP_SPLIT_RULE64 else (ops.split_gemm_ok(C) and ops.split_gemm_ok(Hd)))
+    odt = "split" if split else prec.adt
+    xn2, mean, rstd = ops.layernorm(XT2, g2, b2n, eps, prec, save_stats=keep, out_dtype=odt)
+    w1 = ops.pack_linear([W1], pe, tag + ('fc1',), split=split)
+    w2 = ops.pack_linear([W2], pe, tag + ('fc2',), split=split)
+    # what the backward's GELU' needs.  fp32-class backward (x3): the pre-activation z in fp32, GELU'(z) evaluated in the fc2 dgrad
+    # epilogue.  bf16 backward (bf16, x3f): GELU'(z) itself, taken HERE where z is in registers in fp32 and stored as bf16 (the same
+    # bytes as bf16(z)) — the fc2 dgrad epilogue is then one multiply per element instead of an erf + exp evaluation on 64 890 x 4 096
+    # elements per block (GELU_DAUX: the derivative with the forward, round 6)
+    z = torch.empty(B * N, Hd, dtype=prec.bwd.adt, device=XT2.device) if keep else None
+    daux = keep and GELU_DAUX and z.dtype == torch.bfloat16
+    hmid = ops.linear(xn2, w1, Hd, pe, bias=b1[None], act=ACT_GELU_DAUX if daux else ACT_GELU, aux_out=z, out_dtype=odt)[0]
+    XT3 = torch.empty_like(XT2)
+    rows = dict(d_rows=(N, N * C, C), M=B * N) if keep or rowscale is not None else {}
+    ops.linear(hmid, w2, C, pe, bias=b2[None], out=XT3, resid=XT2, rowscale=rowscale, n_prompt=T, **rows)
+    saved = (XT2, g2, mean, rstd, ops._hi(xn2), z, ops._hi(hmid), ops._hi(w1), ops._hi(w2), rowscale) if keep else None
+    return XT3, saved
+
+
 class AttnHalfFn(Function):
     """First half of a ViT block in ONE autograd node: norm1 -> qkv GEMM -> flash attention (+ prompt-row logits) -> proj GEMM +
     residual [-> channel attention on the prompt rows] (taskprompter.py:195-254, :273-276; vit.py:199-202 without prompts).
@@ -319,46 +408,9 @@ class AttnHalfFn(Function):
 
     @staticmethod
     def forward(ctx, XT, g1, b1, eps, Wqkv, bqkv, Wproj, bproj, Wtt, btt, Wtt1, btt1, rowscale, geo, prec, tag):
-        B, N, nH, T, h, w, nwin = geo[:7]
-        side = geo[7] if len(geo) > 7 else True              # False: no consumer of this block's channel logits (not a tap): skip that pass
-        C, hw = nH * 64, h * w
-        chan = Wtt is not None
-        split = prec.split                       # x3f: x3 products on pre-split planes (LDS-DMA kernel), bf16 backward on the hi planes
-        if split:
-            xs, mean, rstd = ops.layernorm(XT, g1, b1, eps, prec, save_stats=True, out_dtype="split")
-            xp32 = ops.prompt_rows32(xs, B, N, T, C) if chan else None      # the prompt rows (fp32-class) of the channel attention's Linears
-            wq = ops.pack_linear([Wqkv], prec, tag + ('qkv',), split=True)
-            wp = ops.pack_linear([Wproj], prec, tag + ('proj',), split=True)
-            qkv = ops.linear(xs, wq, 3 * C, prec, bias=bqkv[None], out_dtype="split")[0]
-            ao, rawlog, lse = ops.attention(qkv, B, N, nH, T, prec, want_lse=True)
-            xn_b, xn_c = xs.hi, xs                  # backward operand: the bf16 hi plane; the channel attention reads the planes (no fp32 copy)
-        else:
-            xn, mean, rstd = ops.layernorm(XT, g1, b1, eps, prec, save_stats=True)
-            wq = ops.pack_linear([Wqkv], prec, tag + ('qkv',))
-            wp = ops.pack_linear([Wproj], prec, tag + ('proj',))
-            qkv = ops.linear(xn, wq, 3 * C, prec, bias=bqkv[None])[0]
-            flash = FLASH_BWD and prec.name == "bf16" and qkv.dtype == torch.bfloat16
-            ao, rawlog, lse = ops.attention(qkv, B, N, nH, T, prec, want_lse=flash)
-            xn_b = xn_c = xn
-        XT2 = torch.empty_like(XT)
-        ops.linear(ao, wp, C, prec, bias=bproj[None], out=XT2, resid=XT, d_rows=(N, N * C, C), rowscale=rowscale, n_prompt=T,
-                   M=B * N)
-        cq = wt = wt1 = rawchan = None
-        if chan:
-            wt = ops.pack_linear([Wtt], prec, tag + ('tt',))
-            wt1 = ops.pack_linear([Wtt1], prec, tag + ('tt1',))
-            if split:
-                cq = ops.linear(xp32, wt, hw, prec, bias=btt[None], M=B * T)[0]
-            else:
-                cq = ops.linear(xn_c, wt, hw, prec, bias=btt[None], a_rows=(T, N * C, C), M=B * T)[0]
-            if side:
-                rawchan = ops.chan_logits(cq, xn_c, B, T, N, C, (h, w), (nwin, nwin))
-            pr = XT2.view(B, N, C)[:, :T]
-            ops.linear(cq, wt1, C, prec, bias=btt1[None], out=pr, d_rows=(T, N * C, C), resid=pr, rowscale=rowscale, n_prompt=T,
-                       M=B * T)
-        ctx.save_for_backward(XT, g1, mean, rstd, xn_b, ops._hi(qkv), ops._hi(ao), ops._hi(wq), ops._hi(wp), rowscale, lse, cq, wt, wt1,
-                              xp32 if chan and split else None)
-        ctx.geo, ctx.prec, ctx.eps, ctx.chan = geo, prec, eps, chan
+        (XT2, rawlog, rawchan), saved = attn_half(XT, g1, b1, eps, Wqkv, bqkv, Wproj, bproj, Wtt, btt, Wtt1, btt1, rowscale, geo, prec, tag, keep=True)
+        ctx.save_for_backward(*saved)
+        ctx.geo, ctx.prec, ctx.eps, ctx.chan = geo, prec, eps, Wtt is not None
         ctx.params = (Wqkv, Wproj, Wtt, Wtt1)
         # the two logit side channels are consumed only at the four taps (cal_task_feature); for the other 20 blocks autograd would hand
         # backward() MATERIALISED ZERO gradients for them — and the channel-attention backward kernel (227 us per block at the benchmark's
@@ -434,26 +486,9 @@ class MlpHalfFn(Function):
 
     @staticmethod
     def forward(ctx, XT2, g2, b2n, eps, W1, b1, W2, b2, rowscale, geo, prec, tag):
-        B, N, T = geo
-        C, Hd = W1.shape[1], W1.shape[0]
-        # the split-plane kernel: whole 32-deep K steps (InvPT's 288-channel stage included; else register-staged x3).  MLP_SPLIT_RULE64: the rule of
-        # rounds 3-5 (multiples of 64), for A/B runs
-        split = prec.split and ((C % 64 == 0 and Hd % 64 == 0) if MLP_SPLIT_RULE64 else (ops.split_gemm_ok(C) and ops.split_gemm_ok(Hd)))
-        xn2, mean, rstd = ops.layernorm(XT2, g2, b2n, eps, prec, save_stats=True, out_dtype="split" if split else None)
-        w1 = ops.pack_linear([W1], prec, tag + ('fc1',), split=split)
-        w2 = ops.pack_linear([W2], prec, tag + ('fc2',), split=split)
-        # what the backward's GELU' needs.  fp32-class backward (x3): the pre-activation z in fp32, GELU'(z) evaluated in the fc2 dgrad
-        # epilogue.  bf16 backward (bf16, x3f): GELU'(z) itself, taken HERE where z is in registers in fp32 and stored as bf16 (the same
-        # bytes as bf16(z)) — the fc2 dgrad epilogue is then one multiply per element instead of an erf + exp evaluation on 64 890 x 4 096
-        # elements per block (GELU_DAUX: the derivative with the forward, round 6)
-        z = torch.empty(B * N, Hd, dtype=prec.bwd.adt, device=XT2.device)
-        daux = GELU_DAUX and z.dtype == torch.bfloat16
-        hmid = ops.linear(xn2, w1, Hd, prec, bias=b1[None], act=ACT_GELU_DAUX if daux else ACT_GELU, aux_out=z, out_dtype="split" if split else None)[0]
-        XT3 = torch.empty_like(XT2)
-        ops.linear(hmid, w2, C, prec, bias=b2[None], out=XT3, resid=XT2, d_rows=(N, N * C, C), rowscale=rowscale, n_prompt=T,
-                   M=B * N)
-        ctx.save_for_backward(XT2, g2, mean, rstd, ops._hi(xn2), z, ops._hi(hmid), ops._hi(w1), ops._hi(w2), rowscale)
-        ctx.geo, ctx.prec, ctx.eps, ctx.daux = geo, prec, eps, daux
+        XT3, saved = mlp_half(XT2, g2, b2n, eps, W1, b1, W2, b2, rowscale, geo, prec, tag, keep=True)
+        ctx.save_for_backward(*saved)
+        ctx.geo, ctx.prec, ctx.eps, ctx.daux = geo, prec, eps, GELU_DAUX and saved[5].dtype == torch.bfloat16      # (saved[5] = fc1's side output)
         ctx.params = (W1, W2)
         return XT3
 
@@ -475,19 +510,37 @@ class MlpHalfFn(Function):
         return dXT2, dg2, dbn2, None, dW1, db1, dW2, db2, None, None, None, None
 
 
+def block_attn(keep, gp, *args):
+    """a block's first half on AttnHalfFn's arguments -> (XT2, rawlog, rawchan): the autograd node (keep), else its launches alone"""
+    return AttnHalfFn.apply(*args) if keep else attn_half(*args, keep=False, gp=gp)[0]
+
+
+def block_mlp(keep, pe, *args):
+    """a block's second half on MlpHalfFn's arguments -> XT3"""
+    return MlpHalfFn.apply(*args) if keep else mlp_half(*args, keep=False, pe=pe)[0]
+
+
+def patch_embed(img, Wpe, bpe, pos, first, geo, prec, tag, pe=None):
+    """The launches of PatchEmbedFn / invpt_autograd.VitEmbedFn -> (token buffer XT [B*N, C] fp32 with the rows `first` (prompts; class
+    token + its position) in front of every image's patches, the patch columns the weight gradient reads).  Nothing here exists for a
+    backward only, so a forward nobody differentiates calls it as it is.  pe = the 'enc' operand precision of an attribution run."""
+    B, N, T, hw = geo
+    C = Wpe.shape[0]
+    XT = torch.empty(B * N, C, dtype=torch.float32, device=img.device)
+    XT.view(B, N, C)[:, :T] = first
+    cols = ops.patchify(img.float(), prec)
+    wpe = ops.pack_linear([Wpe], pe or prec, tag)
+    ops.linear(cols, wpe, C, pe or prec, bias=bpe[None], out=XT.view(B, N, C)[:, T:], d_rows=(hw, N * C, C),
+               resid=pos[0, 1:], r_rows=(hw, 0, C), M=B * hw)
+    return XT, cols
+
+
 class PatchEmbedFn(Function):
     """patchify + k=s=16 conv as GEMM + pos-embed add, prompts copied in front (taskprompter.py:393-397)."""
 
     @staticmethod
     def forward(ctx, img, Wpe, bpe, pos, prompts, geo, prec):
-        B, N, T, hw = geo
-        C = Wpe.shape[0]
-        XT = torch.empty(B * N, C, dtype=torch.float32, device=img.device)
-        XT.view(B, N, C)[:, :T] = prompts
-        cols = ops.patchify(img.float(), prec)
-        wpe = ops.pack_linear([Wpe], prec, 'pe')
-        ops.linear(cols, wpe, C, prec, bias=bpe[None], out=XT.view(B, N, C)[:, T:], d_rows=(hw, N * C, C),
-                   resid=pos[0, 1:], r_rows=(hw, 0, C), M=B * hw)
+        XT, cols = patch_embed(img, Wpe, bpe, pos, prompts, geo, prec, 'pe')
         ctx.save_for_backward(cols)
         ctx.geo, ctx.prec, ctx.wshape = geo, prec, Wpe.shape
         return XT
@@ -1152,8 +1205,12 @@ def _bn_act(y, bns, C, act, training):
     return BnActStackFn.apply(y, C, act, training, list(bns), *[bn.weight for bn in bns], *[bn.bias for bn in bns])
 
 
-def _task_features(model, xsrc, rawlog, rawchan, il, B, acc):
+def _task_features(model, xsrc, rawlog, rawchan, il, B, acc, keep):
+    """cal_task_feature of one tap (taskprompter.py:424-487), all tasks at once.  The front — modulate -> fea_decode_* -> fea_fuse[0] — is
+    one statement (its Functions compute nothing for a backward that a plain forward would not); after it the schedules differ: the
+    autograd tail (keep) or TaskPrompter._fuse_tail (BatchNorm folded into the conv epilogue in eval, planes for fea_fuse[4])."""
     p, prec = model.p, model.prec
+    ps, pf, adt = model._gp('side'), model._gp('fuse'), prec.adt     # fea_decode_* belong to 'side', fea_fuse to 'fuse' (== prec unless attributing)
     names = p.TASKS.NAMES
     T, C = len(names), model.embed_dim
     h, w = model.resolution
@@ -1168,16 +1225,20 @@ def _task_features(model, xsrc, rawlog, rawchan, il, B, acc):
     for t in names:
         dec_w += [model.fea_decode_spa[il][t][0].weight, model.fea_decode_chan[il][t][0].weight]
         dec_b += [model.fea_decode_spa[il][t][0].bias, model.fea_decode_chan[il][t][0].bias]
-    cat = BLinearFn.apply(mod, tar, 'catpair', None, "split" if sp else None, prec, ('dec', il), mod_lo, *dec_w, *dec_b)
+    cat = BLinearFn.apply(mod, tar, 'catpair', None, "split" if sp else adt, ps, ('dec', il), mod_lo, *dec_w, *dec_b)
     cat, cat_lo = cat if sp else (cat, None)
     del mod, mod_lo
     ff = [model.fea_fuse[il][t] for t in names]
+    # fea_fuse[0] reads torch.cat([spa, chan], 1) (:471): its K = 2*tar columns land at 0 and pitch(tar) of the padded concatenation
     kmap = (2 * tarp, [(0, 0, tar), (tarp, tar, tar)])
     spc = model._decoder_conv_split()    # ... and fea_fuse[0]'s epilogue writes y0 as planes for the implicit-GEMM 3x3 on the same kernel
-    y0 = BLinearFn.apply(cat, F, 'plain', kmap, "split" if spc else (torch.float32 if sp else None), prec, ('f0', il), cat_lo,
+    y0 = BLinearFn.apply(cat, F, 'plain', kmap, "split" if spc else adt, pf, ('f0', il), cat_lo,
                          *[m[0].weight for m in ff], *[m[0].bias for m in ff])
     y0, y0_lo = y0 if spc else (y0, None)
     del cat, cat_lo
+    if not keep:
+        fea = model._fuse_tail(ops.Split(y0, y0_lo) if spc else y0, il, B)
+        return ops.ctr_mix(fea, model._ctr_weights(rawlog, il, B, T), B, F, acc)
     geo1 = (B, h, w, F, F) + ((1, y0_lo) if spc else ())
     if FUSE_HEAD_NODE:
         bns = [m[2] for m in ff]
@@ -1188,38 +1249,43 @@ def _task_features(model, xsrc, rawlog, rawchan, il, B, acc):
         y1 = Conv3x3Fn.apply(y0, geo1, prec, ('f1', il), *[m[1].weight for m in ff], *[m[1].bias for m in ff])
         y1 = _bn_act(y1, [m[2] for m in ff], F, ACT_GELU, model.training)
         fea = BLinearFn.apply(y1, F, 'plain', None, None, prec, ('f4', il), None, *[m[4].weight for m in ff], *[m[4].bias for m in ff])
-    wmix = model._ctr_weights(rawlog, il, B, T)
-    return CtrMixFn.apply(fea, wmix, acc, B, F)
+    return CtrMixFn.apply(fea, model._ctr_weights(rawlog, il, B, T), acc, B, F)
 
 
-def backbone_forward(model, img, upsample=True):
-    """Autograd twin of TaskPrompter._forward_nograd -> [T, B*4h*4w, pitch(F)] task features (upsample=False: the fp32 h x w sums
-    [T, B*h*w, pitch(F)] before the x4 resize, for heads that fuse it)."""
-    p, prec = model.p, model.prec
+def backbone_forward(model, img, upsample, keep):
+    """TaskPrompter's forward -> [T, B*4h*4w, pitch(F)] task features (upsample=False: the fp32 h x w sums [T, B*h*w, pitch(F)] before the
+    x4 resize, for heads that fuse it).  keep: somebody will differentiate it — the encoder then runs as autograd nodes around the same
+    launches; otherwise their bodies alone, with the operand precisions of an attribution run (model._gp) if one is configured."""
+    prec = model.prec
     B = img.shape[0]
-    assert tuple(img.shape[-2:]) == tuple(model.patch_embed.img_size)
+    assert tuple(img.shape[-2:]) == tuple(model.patch_embed.img_size), "input size must equal img_size (timm PatchEmbed assert)"
     h, w = model.resolution
     hw, T, C, nH = h * w, model.prompts_len, model.embed_dim, model.num_heads
     N = T + hw
     nwin = int(math.isqrt(model.chan_nheads))
-    XT = PatchEmbedFn.apply(img, model.patch_embed.proj.weight, model.patch_embed.proj.bias, model.pos_embed,
-                            model.task_prompts, (B, N, T, hw), prec)
+    assert h % nwin == 0 and w % nwin == 0
+    assert not (keep and model.gprec), "mtt_prec_groups is inference-only"
+    gp = (model._gp('enc'), model._gp('attn'), model._gp('side'))
+    # patch embed + pos embed straight into the token buffer; prompts first
+    embed = (img, model.patch_embed.proj.weight, model.patch_embed.proj.bias, model.pos_embed, model.task_prompts, (B, N, T, hw), prec)
+    XT = PatchEmbedFn.apply(*embed) if keep else patch_embed(*embed, 'pe', pe=gp[0])[0]
     acc = None
     rawlog = rawchan = None
-    drops = _drop_tables(model, B, img.device)
+    # DropPath only where a backward is kept (DESIGN.md, open items: the reference also drops in a train-mode forward without gradients)
+    drops = _drop_tables(model, B, img.device) if keep else [(None, None)] * len(model.blocks)
     for i, blk in enumerate(model.blocks):
         a = blk.attn
         rs_attn, rs_mlp = drops[i]
-        XT2, rawlog, rawchan = AttnHalfFn.apply(XT, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, a.qkv.weight, a.qkv.bias,
-                                                a.proj.weight, a.proj.bias, a.token_trans.weight, a.token_trans.bias,
-                                                a.token_trans1.weight, a.token_trans1.bias, rs_attn,
-                                                (B, N, nH, T, h, w, nwin, model._side_channels_used(i)), prec, ('blk', i))
-        XT = MlpHalfFn.apply(XT2, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, blk.mlp.fc1.weight, blk.mlp.fc1.bias,
-                             blk.mlp.fc2.weight, blk.mlp.fc2.bias, rs_mlp, (B, N, T), prec, ('blk', i))
+        # the residual stream is rebound half by half: without a backward, a half's input is freed as soon as its output exists
+        XT, rawlog, rawchan = block_attn(keep, gp, XT, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, a.qkv.weight, a.qkv.bias,
+                                         a.proj.weight, a.proj.bias, a.token_trans.weight, a.token_trans.bias, a.token_trans1.weight,
+                                         a.token_trans1.bias, rs_attn, (B, N, nH, T, h, w, nwin, model._side_channels_used(i)), prec, ('blk', i))
+        XT = block_mlp(keep, gp[0], XT, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, blk.mlp.fc1.weight, blk.mlp.fc1.bias,
+                       blk.mlp.fc2.weight, blk.mlp.fc2.bias, rs_mlp, (B, N, T), prec, ('blk', i))
         if (i + 1) in model.select_list:
-            acc = _task_features(model, XT, rawlog, rawchan, model._tap_index(i), B, acc)
-    xf = LayerNormFn.apply(XT, model.norm.weight, model.norm.bias, model.norm.eps, prec, torch.float32)
-    acc = _task_features(model, xf, rawlog, rawchan, 3, B, acc)
+            acc = _task_features(model, XT, rawlog, rawchan, model._tap_index(i), B, acc, keep)
+    xf = layernorm(XT, model.norm.weight, model.norm.bias, model.norm.eps, prec, torch.float32, keep)
+    acc = _task_features(model, xf, rawlog, rawchan, 3, B, acc, keep)
     return upsample4(acc, B, h, w, prec) if upsample else acc
 
 

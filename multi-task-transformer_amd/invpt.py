@@ -13,8 +13,9 @@ Schedule (differs from the reference's op graph):
   * Dead reference compute is skipped (scale_embed[2], norm_mt, stage-0 fuse_attn, redu_chan[0]); their parameters
     exist (strict state_dict) and — as in the reference — receive no gradient.
 
-This file is the no-grad forward (eval and train-mode BatchNorm statistics); with gradients enabled the same
-modules route to invpt_autograd.py (autograd Functions with hand-written backward on the same kernels).
+This file holds the modules and the decoder's no-grad forward (eval and train-mode BatchNorm statistics).  The ViT has one
+forward for inference and training (invpt_autograd.vit_taps); with gradients enabled the decoder routes to invpt_autograd.py
+(autograd Functions with hand-written backward on the same kernels).
 """
 import math
 from collections import OrderedDict
@@ -91,45 +92,9 @@ class VisionTransformer(nn.Module):
 
     def forward_taps(self, img):
         """-> 4 contiguous [B*hw, C] activation-dtype token maps (cls dropped), vit.py:340-349."""
-        if torch.is_grad_enabled() and (img.requires_grad or any(q.requires_grad for q in self.parameters())):
-            from . import invpt_autograd
-            return invpt_autograd.vit_taps(self, img)
-        prec = self.prec
-        B = img.shape[0]
-        C, nH = self.embed_dim, self.num_heads
-        hw = self.patch_embed.num_patches
-        N = hw + 1
-        XT = torch.empty(B * N, C, dtype=torch.float32, device=img.device)
-        XT.view(B, N, C)[:, :1] = (self.cls_token + self.pos_embed[:, :1]).detach()
-        cols = ops.patchify(img.float(), prec)
-        ops.linear(cols, ops.pack_linear([self.patch_embed.proj.weight], prec, 'vpe'), C, prec,
-                   bias=self.patch_embed.proj.bias.detach()[None], out=XT.view(B, N, C)[:, 1:], d_rows=(hw, N * C, C),
-                   resid=self.pos_embed.detach()[0, 1:], r_rows=(hw, 0, C), M=B * hw)
-        taps = []
-        # x3f: the four big Linears of a block on the split-plane LDS-DMA kernel (operands written as hi / lo planes by LayerNorm, the
-        # qkv / fc1 epilogues and the attention kernel), as TaskPrompter._block_split; the K = C reductions must be whole 32-deep steps
-        split = prec.split and C % 32 == 0
-
-        def pack(ws, tg):
-            return ops.pack_linear(ws, prec, tg, split=split)
-        sp = dict(out_dtype="split") if split else {}
-        for i, blk in enumerate(self.blocks):
-            tag = ('vblk', i)
-            xn, _, _ = ops.layernorm(XT, blk.norm1.weight.detach(), blk.norm1.bias.detach(), blk.norm1.eps, prec, **sp)
-            qkv = ops.linear(xn, pack([blk.attn.qkv.weight], tag + ('qkv',)), 3 * C, prec, bias=blk.attn.qkv.bias.detach()[None], **sp)[0]
-            ao, _, _ = ops.attention(qkv, B, N, nH, 0, prec)
-            XT2 = torch.empty_like(XT)
-            ops.linear(ao, pack([blk.attn.proj.weight], tag + ('proj',)), C, prec, bias=blk.attn.proj.bias.detach()[None], out=XT2, resid=XT)
-            xn2, _, _ = ops.layernorm(XT2, blk.norm2.weight.detach(), blk.norm2.bias.detach(), blk.norm2.eps, prec, **sp)
-            hmid = ops.linear(xn2, pack([blk.mlp.fc1.weight], tag + ('fc1',)), 4 * C, prec, bias=blk.mlp.fc1.bias.detach()[None],
-                              act=ACT_GELU, **sp)[0]
-            XT = torch.empty_like(XT)
-            ops.linear(hmid, pack([blk.mlp.fc2.weight], tag + ('fc2',)), C, prec, bias=blk.mlp.fc2.bias.detach()[None], out=XT, resid=XT2)
-            if (i + 1) in self.select_list:
-                taps.append(XT.view(B, N, C)[:, 1:].to(prec.adt).reshape(B * hw, C))
-        xf, _, _ = ops.layernorm(XT, self.norm.weight.detach(), self.norm.bias.detach(), self.norm.eps, prec)
-        taps.append(xf.view(B, N, C)[:, 1:].reshape(B * hw, C).contiguous())
-        return taps
+        from . import invpt_autograd
+        keep = torch.is_grad_enabled() and (img.requires_grad or any(q.requires_grad for q in self.parameters()))
+        return invpt_autograd.vit_taps(self, img, keep)
 
 
 def _create_vision_transformer(variant, pretrained=False, default_cfg=None, **kwargs):

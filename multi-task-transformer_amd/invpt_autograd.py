@@ -1,6 +1,6 @@
 """Training path of InvPT (InvPT/models/transformers/vit.py, transformer_decoder.py, invpt.py,
-InvPT/models/transformer_net.py): the schedule of invpt.py's no-grad forward rebuilt from
-torch.autograd.Functions whose forward AND backward run on the libmtt_hip.so kernels.
+InvPT/models/transformer_net.py): the ViT's one forward (vit_taps, also what inference runs) and the schedule of
+invpt.py's no-grad decoder rebuilt from torch.autograd.Functions whose forward AND backward run on the libmtt_hip.so kernels.
 
 Shared with the TaskPrompter training path (autograd_path.py): LayerNormFn, AttnHalfFn (no prompt rows),
 MlpHalfFn, BLinearFn, Conv3x3Fn (dilated, bias-free), BnActStackFn, BilinearFn.  New here: the ViT patch embed with a
@@ -17,25 +17,25 @@ from torch.autograd import Function
 from . import ops
 from ._lib import ACT_NONE, ACT_RELU, F32, OP_K, OP_R, dtype_code
 from . import autograd_path
-from .autograd_path import (AttnHalfFn, MlpHalfFn, BLinearFn, BilinearFn, Conv3x3Fn, ConvHeadFn, LayerNormFn, TaskHeadsFn, _bn_act,
-                            _colsum, _dgrad, _gemm, _wgrad)
+from .autograd_path import (MlpHalfFn, BLinearFn, BilinearFn, Conv3x3Fn, ConvHeadFn, LayerNormFn, TaskHeadsFn, _bn_act,
+                            _colsum, _dgrad, _gemm, _wgrad, block_attn, block_mlp, patch_embed)
 
 pitch = ops.pitch
 
 
 # =================================================================================================
+def vit_embed(img, Wpe, bpe, pos, cls, geo, prec):
+    """VitEmbedFn's launches -> (XT, patch columns): autograd_path.patch_embed with the class token + its position in row 0"""
+    B, N, hw = geo
+    return patch_embed(img, Wpe, bpe, pos, cls + pos[:, :1], (B, N, 1, hw), prec, 'vpe')
+
+
 class VitEmbedFn(Function):
     """patchify + k=s=16 conv as GEMM + pos-embed add, class token in row 0 (vit.py:326-333)."""
 
     @staticmethod
     def forward(ctx, img, Wpe, bpe, pos, cls, geo, prec):
-        B, N, hw = geo
-        C = Wpe.shape[0]
-        XT = torch.empty(B * N, C, dtype=torch.float32, device=img.device)
-        XT.view(B, N, C)[:, :1] = cls + pos[:, :1]
-        cols = ops.patchify(img.float(), prec)
-        ops.linear(cols, ops.pack_linear([Wpe], prec, 'vpe'), C, prec, bias=bpe[None], out=XT.view(B, N, C)[:, 1:],
-                   d_rows=(hw, N * C, C), resid=pos[0, 1:], r_rows=(hw, 0, C), M=B * hw)
+        XT, cols = vit_embed(img, Wpe, bpe, pos, cls, geo, prec)
         ctx.save_for_backward(cols)
         ctx.geo, ctx.prec, ctx.wshape = geo, prec, Wpe.shape
         return XT
@@ -317,24 +317,27 @@ def _check8(*dims):
                                   f"{ops.PITCH32_FROM} channels on), got {dims}")
 
 
-def vit_taps(vit, img):
-    """Autograd twin of VisionTransformer.forward_taps (vit.py:326-349)."""
+def vit_taps(vit, img, keep):
+    """VisionTransformer.forward_taps (vit.py:326-349): the ViT's one forward.  keep: somebody will differentiate it (autograd nodes around
+    the launches); otherwise the same launches alone (autograd_path.block_attn / block_mlp).  x3f: the four big Linears of a block on the
+    split-plane LDS-DMA kernel, operands written as hi / lo planes by LayerNorm, the qkv / fc1 epilogues and the attention kernel."""
     prec = vit.prec
     B = img.shape[0]
     C, nH = vit.embed_dim, vit.num_heads
     hw = vit.patch_embed.num_patches
     N = hw + 1
-    XT = VitEmbedFn.apply(img, vit.patch_embed.proj.weight, vit.patch_embed.proj.bias, vit.pos_embed, vit.cls_token, (B, N, hw), prec)
+    embed = (img, vit.patch_embed.proj.weight, vit.patch_embed.proj.bias, vit.pos_embed, vit.cls_token, (B, N, hw), prec)
+    XT = VitEmbedFn.apply(*embed) if keep else vit_embed(*embed)[0]
     taps = []
     for i, blk in enumerate(vit.blocks):
         a = blk.attn
-        XT2, _, _ = AttnHalfFn.apply(XT, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, a.qkv.weight, a.qkv.bias, a.proj.weight,
-                                     a.proj.bias, None, None, None, None, None, (B, N, nH, 0, 0, 0, 1), prec, ('vblk', i))
-        XT = MlpHalfFn.apply(XT2, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, blk.mlp.fc1.weight, blk.mlp.fc1.bias,
-                             blk.mlp.fc2.weight, blk.mlp.fc2.bias, None, (B, N, 0), prec, ('vblk', i))
+        XT = block_attn(keep, None, XT, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
+                        None, None, None, None, None, (B, N, nH, 0, 0, 0, 1), prec, ('vblk', i))[0]
+        XT = block_mlp(keep, None, XT, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, blk.mlp.fc1.weight, blk.mlp.fc1.bias,
+                       blk.mlp.fc2.weight, blk.mlp.fc2.bias, None, (B, N, 0), prec, ('vblk', i))
         if (i + 1) in vit.select_list:
             taps.append(XT.view(B, N, C)[:, 1:].to(prec.adt).reshape(B * hw, C))
-    xf = LayerNormFn.apply(XT, vit.norm.weight, vit.norm.bias, vit.norm.eps, prec, None)
+    xf = autograd_path.layernorm(XT, vit.norm.weight, vit.norm.bias, vit.norm.eps, prec, None, keep)
     taps.append(xf.view(B, N, C)[:, 1:].reshape(B * hw, C))
     return taps
 
@@ -473,7 +476,7 @@ def net_forward(net, x):
     B = x.shape[0]
     dec = net.multi_task_decoder
     prec = dec.prec
-    taps = vit_taps(net.backbone, x)
+    taps = vit_taps(net.backbone, x, True)
     hds = [net.heads[t] for t in net.tasks]
     preds, inter = decoder_forward(dec, taps, B, heads=hds)
     mh, mw = net.p.mtt_resolution

@@ -217,10 +217,9 @@ class TaskPrompter(nn.Module):
     def forward_nhwc(self, img, upsample=True):
         """-> [T, B*4h*4w, pitch(F)] activation-dtype task features (x4-upsampled sum over the 4 taps; taskprompter.py:420).
         upsample=False stops before the resize: fp32 [T, B*h*w, pitch(F)], for heads that fuse it into their first conv."""
-        if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
-            from . import autograd_path
-            return autograd_path.backbone_forward(self, img, upsample)
-        return self._forward_nograd(img, upsample)
+        from . import autograd_path
+        keep = torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters())       # will anybody differentiate this forward?
+        return autograd_path.backbone_forward(self, img, upsample, keep)
 
     def upsample4(self, acc, B):
         """the x4 bilinear resize of forward_nhwc(upsample=False)'s result (differentiable when that is)."""
@@ -230,132 +229,28 @@ class TaskPrompter(nn.Module):
             return autograd_path.upsample4(acc, B, h, w, self.prec)
         return ops.bilinear(acc, B, acc.shape[-1], h, w, 4 * h, 4 * w, self.prec.adt)
 
-    def _forward_nograd(self, img, upsample=True):
-        p, prec = self.p, self.prec
-        B = img.shape[0]
-        H, W = img.shape[-2:]
-        assert (H, W) == tuple(self.patch_embed.img_size), "input size must equal img_size (timm PatchEmbed assert)"
+    # ---- cal_task_feature (taskprompter.py:424-487), all tasks at once: autograd_path._task_features + -----
+    def _fuse_tail(self, y0, il, B):
+        """fea_fuse[1..4] of one tap in a forward nobody differentiates (the front and the autograd tail: autograd_path._task_features):
+        y0 = fea_fuse[0]'s output [T, B*h*w, pitch(F)] (planes when _decoder_conv_split) -> the task features before the cross-task mix."""
+        names, F = self.p.TASKS.NAMES, self.p.final_embed_dim
+        pf, adt = self._gp('fuse'), self.prec.adt
         h, w = self.resolution
-        hw, T, C, nH = h * w, self.prompts_len, self.embed_dim, self.num_heads
-        N = T + hw
-        dev = img.device
-        nwin = int(math.isqrt(self.chan_nheads))
-        assert h % nwin == 0 and w % nwin == 0
-
-        # ---- patch embed + pos embed straight into the token buffer; prompts first ----------------
-        XT = torch.empty(B * N, C, dtype=torch.float32, device=dev)
-        XT.view(B, N, C)[:, :T] = self.task_prompts.detach()
-        cols = ops.patchify(img.float(), prec)
-        pe = self._gp('enc')
-        wpe = ops.pack_linear([self.patch_embed.proj.weight], pe, 'pe')
-        ops.linear(cols, wpe, C, pe, bias=self.patch_embed.proj.bias.detach()[None], out=XT.view(B, N, C)[:, T:],
-                   d_rows=(hw, N * C, C), resid=self.pos_embed.detach()[0, 1:], r_rows=(hw, 0, C), M=B * hw)
-
-        acc = None
-        rawlog = rawchan = None
-        for i, blk in enumerate(self.blocks):
-            XT, rawlog, rawchan = self._block(blk, i, XT, B, N, T, (h, w), nwin)
-            if (i + 1) in self.select_list:
-                acc = self._task_features(XT, XT.view(B, N, C)[:, T:], rawlog, rawchan, self._tap_index(i), B, acc)
-        xf, _, _ = ops.layernorm(XT, self.norm.weight.detach(), self.norm.bias.detach(), self.norm.eps, prec,
-                                 out_dtype=torch.float32)
-        acc = self._task_features(xf, xf.view(B, N, C)[:, T:], rawlog, rawchan, 3, B, acc)
-        return ops.bilinear(acc, B, acc.shape[-1], h, w, 4 * h, 4 * w, prec.adt) if upsample else acc
-
-    def _block(self, blk, i, XT, B, N, T, grid, nwin):
-        prec, C, nH = self.prec, self.embed_dim, self.num_heads
-        pe, pa, ps = self._gp('enc'), self._gp('attn'), self._gp('side')
-        adt = prec.adt                                              # storage dtype (a group override only changes operand rounding)
-        hw = grid[0] * grid[1]
-        a = blk.attn
-        tag = ('blk', i)
-        if prec.split and self.gprec is None:
-            return self._block_split(blk, tag, XT, B, N, T, grid, nwin, self._side_channels_used(i))
-        xn, _, _ = ops.layernorm(XT, blk.norm1.weight.detach(), blk.norm1.bias.detach(), blk.norm1.eps, prec)
-        qkv = ops.linear(xn, ops.pack_linear([a.qkv.weight], pe, tag + ('qkv',)), 3 * C, pe,
-                         bias=a.qkv.bias.detach()[None], out_dtype=adt)[0]
-        if pa.adt != qkv.dtype:                                      # attribution: bf16 attention inside an fp32-storage run
-            q16 = ops.cast2d(qkv, qkv.shape[0], 3 * C, 3 * C, pa.adt, ldd=3 * C)
-            ao16, rawlog, _ = ops.attention(q16, B, N, nH, T, pa)
-            ao = ops.cast2d(ao16, ao16.shape[0], C, C, adt, ldd=C)
-        else:
-            ao, rawlog, _ = ops.attention(qkv, B, N, nH, T, pa)
-        XT2 = torch.empty_like(XT)
-        ops.linear(ao, ops.pack_linear([a.proj.weight], pe, tag + ('proj',)), C, pe, bias=a.proj.bias.detach()[None],
-                   out=XT2, resid=XT)
-        # channel attention: queries token_trans(norm1(prompts)), keys norm1(x)^T, windowed (:216-250)
-        cq = ops.linear(xn, ops.pack_linear([a.token_trans.weight], ps, tag + ('tt',)), hw, ps,
-                        bias=a.token_trans.bias.detach()[None], a_rows=(T, N * C, C), M=B * T, out_dtype=ps.adt)[0]
-        rawchan = None
-        if self._side_channels_used(i):
-            xnc = xn if ps.adt == xn.dtype else ops.cast2d(xn, xn.shape[0], C, C, ps.adt, ldd=C)
-            rawchan = ops.chan_logits(cq, xnc, B, T, N, C, grid, (nwin, nwin))
-        pr = XT2.view(B, N, C)[:, :T]
-        ops.linear(cq, ops.pack_linear([a.token_trans1.weight], ps, tag + ('tt1',)), C, ps,
-                   bias=a.token_trans1.bias.detach()[None], out=pr, d_rows=(T, N * C, C), resid=pr, M=B * T)
-        xn2, _, _ = ops.layernorm(XT2, blk.norm2.weight.detach(), blk.norm2.bias.detach(), blk.norm2.eps, prec)
-        hmid = ops.linear(xn2, ops.pack_linear([blk.mlp.fc1.weight], pe, tag + ('fc1',)), 4 * C, pe,
-                          bias=blk.mlp.fc1.bias.detach()[None], act=ACT_GELU, out_dtype=adt)[0]
-        XT3 = torch.empty_like(XT)
-        ops.linear(hmid, ops.pack_linear([blk.mlp.fc2.weight], pe, tag + ('fc2',)), C, pe,
-                   bias=blk.mlp.fc2.bias.detach()[None], out=XT3, resid=XT2)
-        return XT3, rawlog, rawchan
-
-    def _block_split(self, blk, tag, XT, B, N, T, grid, nwin, side=True):
-        """the block in the x3f mode (inference): the same x3 products, the four big Linears on the LDS-DMA kernel over pre-split
-        hi / lo planes (ops.Split) written by the producing kernels (LayerNorm, qkv / fc1 epilogues, attention)."""
-        prec, C, nH = self.prec, self.embed_dim, self.num_heads
-        hw = grid[0] * grid[1]
-        a = blk.attn
-        xs, _, _ = ops.layernorm(XT, blk.norm1.weight.detach(), blk.norm1.bias.detach(), blk.norm1.eps, prec, out_dtype="split")
-        qkv = ops.linear(xs, ops.pack_linear([a.qkv.weight], prec, tag + ('qkv',), split=True), 3 * C, prec, bias=a.qkv.bias.detach()[None],
-                         out_dtype="split")[0]
-        ao, rawlog, _ = ops.attention(qkv, B, N, nH, T, prec)
-        XT2 = torch.empty_like(XT)
-        ops.linear(ao, ops.pack_linear([a.proj.weight], prec, tag + ('proj',), split=True), C, prec, bias=a.proj.bias.detach()[None], out=XT2, resid=XT)
-        # channel attention: its patch rows are read as the planes LayerNorm wrote (no fp32 copy of the normalised tokens), its T prompt rows
-        # per image are gathered into a small fp32 matrix
-        cq = ops.linear(ops.prompt_rows32(xs, B, N, T, C), ops.pack_linear([a.token_trans.weight], prec, tag + ('tt',)), hw, prec,
-                        bias=a.token_trans.bias.detach()[None], M=B * T)[0]
-        rawchan = ops.chan_logits(cq, xs, B, T, N, C, grid, (nwin, nwin)) if side else None
-        pr = XT2.view(B, N, C)[:, :T]
-        ops.linear(cq, ops.pack_linear([a.token_trans1.weight], prec, tag + ('tt1',)), C, prec,
-                   bias=a.token_trans1.bias.detach()[None], out=pr, d_rows=(T, N * C, C), resid=pr, M=B * T)
-        xs2, _, _ = ops.layernorm(XT2, blk.norm2.weight.detach(), blk.norm2.bias.detach(), blk.norm2.eps, prec, out_dtype="split")
-        hmid = ops.linear(xs2, ops.pack_linear([blk.mlp.fc1.weight], prec, tag + ('fc1',), split=True), 4 * C, prec,
-                          bias=blk.mlp.fc1.bias.detach()[None], act=ACT_GELU, out_dtype="split")[0]
-        XT3 = torch.empty_like(XT)
-        ops.linear(hmid, ops.pack_linear([blk.mlp.fc2.weight], prec, tag + ('fc2',), split=True), C, prec,
-                   bias=blk.mlp.fc2.bias.detach()[None], out=XT3, resid=XT2)
-        return XT3, rawlog, rawchan
-
-    # ---- cal_task_feature (taskprompter.py:424-487), all tasks at once -----------------------------
-    def _decoder_packs(self, il):
-        p = self.p
-        prec, pf = self._gp('side'), self._gp('fuse')          # fea_decode_* belong to 'side', fea_fuse to 'fuse' (== self.prec unless attributing)
-        names = p.TASKS.NAMES
-        tar, F = p.embed_dim, p.final_embed_dim
-        tarp = ops.pitch(tar)
-        dec_w, dec_b = [], []
-        for t in names:
-            dec_w += [self.fea_decode_spa[il][t][0].weight, self.fea_decode_chan[il][t][0].weight]
-            dec_b += [self.fea_decode_spa[il][t][0].bias, self.fea_decode_chan[il][t][0].bias]
-        bdec = ops.stack_vec(dec_b, ('decb', il))
-        f0 = [self.fea_fuse[il][t][0].weight for t in names]
-        # fea_fuse[0] reads torch.cat([spa, chan], 1) (:471): its K = 2*tar columns land at 0 and pitch(tar) of the padded concatenation
-        sp = self._decoder_split()
-        Wdec = ops.pack_linear(dec_w, prec, ('dec', il), split=sp)
-        W0 = ops.pack_kmap(f0, F, 2 * tarp, [(0, 0, tar), (tarp, tar, tar)], pf, ('f0', il), split=sp)
-        b0 = ops.stack_vec([self.fea_fuse[il][t][0].bias for t in names], ('f0b', il))
-        fc = [self.fea_fuse[il][t][1].weight for t in names]
-        Wc = ops.pack_conv3(fc, pf, ('f1', il), split=True if self._decoder_conv_split() else None)
-        bc = ops.stack_vec([self.fea_fuse[il][t][1].bias for t in names], ('f1b', il))
-        f4 = [self.fea_fuse[il][t][4].weight for t in names]
+        ff = [self.fea_fuse[il][t] for t in names]
+        Wc = ops.pack_conv3([m[1].weight for m in ff], pf, ('f1', il), split=True if self._decoder_conv_split() else None)
         # inference (BatchNorm folded into the conv's epilogue): the conv writes GELU(BN(.)) as planes, so fea_fuse[4] runs on the split-plane
         # kernel too (880 -> 490 us per tap at B = 63, profiles/r05_dec_x3_bench_b_edge.log); in training BatchNorm's apply writes fp32
-        W4 = ops.pack_linear(f4, pf, ('f4', il), split=self._fuse4_split())
-        b4 = ops.stack_vec([self.fea_fuse[il][t][4].bias for t in names], ('f4b', il))
-        return Wdec, bdec, W0, b0, Wc, bc, W4, b4
+        W4 = ops.pack_linear([m[4].weight for m in ff], pf, ('f4', il), split=self._fuse4_split())
+        b4 = ops.stack_vec([m[4].bias for m in ff], ('f4b', il))
+        bns = [m[2] for m in ff]
+        if self.training:
+            bc = ops.stack_vec([m[1].bias for m in ff], ('f1b', il))
+            y1 = ops.conv3x3(y0, Wc, F, F, B, h, w, pf, bias=bc, out_dtype=adt)
+            y1 = bn_mod.train_forward(y1, F, list(bns), ACT_GELU)[0]
+        else:
+            sc, sh = bn_mod.fold(bns, [m[1].bias for m in ff], ('f2', il))
+            y1 = ops.conv3x3(y0, Wc, F, F, B, h, w, pf, bias=sh, colscale=sc, act=ACT_GELU, out_dtype="split" if self._fuse4_split() else adt)
+        return ops.linear(y1, W4, F, pf, bias=b4, out_dtype=adt)
 
     def _decoder_split(self):
         """x3f: fea_decode_* and fea_fuse[0] on the split-plane LDS-DMA kernel — `modulate` writes hi / lo planes, the fea_decode epilogue
@@ -380,36 +275,6 @@ class TaskPrompter(nn.Module):
         mods = [self.ctr_attn_conv[il][t] for t in self.p.TASKS.NAMES]
         return autograd_path.CtrWeightsFn.apply(rawlog, B, T, ('ctrw', il), *[m[0].weight for m in mods], *[m[0].bias for m in mods],
                                                 *[m[2].weight for m in mods], *[m[2].bias for m in mods])
-
-    def _task_features(self, xsrc, xview, rawlog, rawchan, il, B, acc):
-        p, prec = self.p, self.prec
-        ps, pf, adt = self._gp('side'), self._gp('fuse'), self.prec.adt
-        names = p.TASKS.NAMES
-        T, C = len(names), self.embed_dim
-        h, w = self.resolution
-        hw, N = h * w, T + h * w
-        tar, F = p.embed_dim, p.final_embed_dim
-        tarp, Fp = ops.pitch(tar), ops.pitch(F)
-        nwin = int(math.isqrt(self.chan_nheads))
-        Wdec, bdec, W0, b0, Wc, bc, W4, b4 = self._decoder_packs(il)
-        sp = self._decoder_split()
-        mod = ops.modulate(xview, C, N * C, rawlog, rawchan, B, T, N, C, (h, w), (nwin, nwin), prec, split=sp)
-        cat = ops.Split.empty((T, B * hw, 2 * tarp), xsrc.device) if sp else torch.empty(T, B * hw, 2 * tarp, dtype=prec.adt, device=xsrc.device)
-        ops.linear(mod, Wdec, tar, ps, bias=bdec, out=cat, batch_inner=2, d_z=(B * hw * 2 * tarp, tarp), ldd=2 * tarp,
-                   n_store=tarp)
-        del mod
-        y0 = ops.linear(cat, W0, F, pf, bias=b0, out_dtype="split" if self._decoder_conv_split() else adt)
-        del cat
-        bns = [self.fea_fuse[il][t][2] for t in names]
-        if self.training:
-            y1 = ops.conv3x3(y0, Wc, F, F, B, h, w, pf, bias=bc, out_dtype=adt)
-            y1 = bn_mod.train_forward(y1, F, list(bns), ACT_GELU)[0]
-        else:
-            sc, sh = bn_mod.fold(bns, [self.fea_fuse[il][t][1].bias for t in names], ('f2', il))
-            y1 = ops.conv3x3(y0, Wc, F, F, B, h, w, pf, bias=sh, colscale=sc, act=ACT_GELU, out_dtype="split" if self._fuse4_split() else adt)
-        fea = ops.linear(y1, W4, F, pf, bias=b4, out_dtype=adt)
-        wmix = self._ctr_weights(rawlog, il, B, T).detach()
-        return ops.ctr_mix(fea, wmix, B, F, acc)
 
 
 def _create_task_prompter(variant, pretrained=False, default_cfg=None, **kwargs):

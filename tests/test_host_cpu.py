@@ -60,6 +60,43 @@ def test_wiring_on_emulator_matches_golden(emulated, name, prec, tol):
         assert float((out[t] - g).norm() / g.norm()) < tol, (t, prec)
 
 
+def test_prec_attribution_groups_on_emulator(emulated):
+    """`p.mtt_prec_groups` (tools/prec_attribution.py; fp32 storage, per-group operand precision, inference only) goes through the shared
+    block body.  Every group at 'x3' IS the plain x3 forward (bitwise).  bf16 operands in one of the groups enc / attn / side / fuse alone
+    move every output, by no more than the whole bf16 mode may (4e-2 per head: the bound of test_wiring_on_emulator_matches_golden on
+    this miniature).  Asking for a backward asserts."""
+    import mtt_amd
+    cfg = configs.taskprompter("mini_ctr")
+    meta, _ = conftest.load_golden("mini_ctr")
+    C, depth, nH, sel = configs.VIT[cfg["backbone"]]
+    x = weights.synth_images(meta["batch"], cfg["img_size"], 1)
+
+    def build(groups):
+        extra = dict(mtt_prec_groups=groups) if groups else {}
+        p = mtt_amd.factory.make_p([t for t, _ in cfg["tasks"]], cfg["img_size"], backbone=(C, depth, nH, sel), head=cfg["head"],
+                                   embed_dim=cfg["embed_dim"], final_embed_dim=cfg["final_embed_dim"], chan_nheads=cfg["chan_nheads"],
+                                   use_ctr=cfg["use_ctr"], num_output=dict(cfg["tasks"]), prec="x3", drop_path_rate=0.0, **extra)
+        model = mtt_amd.factory.get_model(p)
+        model.load_state_dict(weights.synth_state_dict(meta["contract"], 0), strict=True)
+        return model.eval()
+
+    def run(groups):
+        with torch.no_grad():
+            return build(groups)(x)
+    plain = run(None)
+    all_x3 = run({g: "x3" for g in mtt_amd.taskprompter.PREC_GROUPS})
+    for t, _ in cfg["tasks"]:
+        assert torch.equal(all_x3[t], plain[t]), t
+    for group in ("enc", "attn", "side", "fuse"):         # ('heads' lives in run_heads, outside the shared bodies)
+        out16 = run({group: "bf16"})
+        for t, _ in cfg["tasks"]:
+            e = float((out16[t] - plain[t]).norm() / plain[t].norm())
+            print(f"{group} bf16 vs x3, {t}: {e:.3e}")
+            assert 0.0 < e < 4e-2, (group, t, e)
+    with pytest.raises(AssertionError, match="inference-only"):
+        build({"attn": "bf16"}).train()(x)
+
+
 @pytest.mark.parametrize("name", ["mini_ctr", "mini_deconv"])
 def test_wiring_train_mode_batchnorm(emulated, name):
     cfg = configs.taskprompter(name)
