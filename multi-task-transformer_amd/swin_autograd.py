@@ -1,33 +1,38 @@
-"""Training (autograd) path of TaskPrompterSwin: the forward of taskprompter_swin.py as a graph of autograd Functions.
+"""TaskPrompterSwin's forward and the autograd nodes of its training path.
 
-First version — correct, not yet fast.  The heavy operators are the HIP building blocks of the ViT variant (LayerNormFn, BLinearFn,
-MlpHalfFn, ModulateFn, Conv3x3Fn, BnActStackFn, BilinearFn) plus four new Functions: window gather (forward and adjoint through the same
-mtt_gather_rows kernel with the inverse tables), window attention (mtt_winattn_fwd / mtt_winattn_bwd; the relative-position-bias
-gradient is the window sum of the kernel's dS, index-added into the table), channel attention (HIP forward; its backward — a few
-hundred thousand elements — is recomputed with torch autograd) and the 3x3 stride-2 convolution of the attention maps (HIP forward,
-torch backward on the 8..96-channel maps).  Residual adds, prompt / pixel row concatenations and the transposed copy feeding chan_kv
-are torch ops here (the inference path has none of them): listed in DESIGN.md as the next things to fuse.  DropPath: the block's four
+`backbone_forward` states the forward of taskprompter_swin.py once — preamble, level loop, task features, multi-scale fusion — for inference
+and training.  `keep` (somebody will differentiate it) picks where there really are two schedules: the block and the patch merging (the
+autograd graph `_block` / `_merge` below, or the in-place TaskPrompterSwin._block / _merge), the patch embed's form, the cast in front of the
+fusion conv and, in eval without gradients, the BatchNorm fold of the task features' tail.  Everything else is a Function applied in both
+cases: under `no_grad` it launches and saves nothing.
+
+The heavy operators are the HIP building blocks of the ViT variant (LayerNormFn, BLinearFn, MlpHalfFn, ModulateFn, Conv3x3Fn,
+BnActStackFn, BilinearFn, MultiScaleSumFn) plus the Functions here: window gather (forward and adjoint through the same mtt_gather_rows
+kernel with the inverse tables), window attention (mtt_winattn_fwd / mtt_winattn_bwd; the relative-position-bias gradient is the window
+sum of the kernel's dS, index-added into the table), channel attention (mtt_chanattn_fwd / _bwd), chan_kv as three GEMMs on the
+token-major rows (ChanKvFn), the block's residual as one node (BlockResidualFn) and the 3x3 stride-2 convolution of the attention maps.
+Prompt / pixel row concatenations are torch ops in the autograd schedule (the in-place one has none).  DropPath: the block's four
 independent per-sample draws (taskprompter_swin.py:408-413) scale the attention branch (pixels / prompts) and, through MlpHalfFn's
 row-scale epilogue, the MLP branch.
 """
 import math
+from functools import partial
 
 import torch
 from torch.autograd import Function
 
+from . import bn as bn_mod
 from . import ops
-from ._lib import ACT_GELU, dtype_code
-from .autograd_path import (BilinearFn, BLinearFn, Conv3x3Fn, LayerNormFn, MlpHalfFn, ModulateFn, _bn_act)
+from . import taskprompter_swin as sw
+from ._lib import ACT_GELU, F32, OP_K, OP_R, dtype_code
+from .autograd_path import (BilinearFn, BLinearFn, Conv3x3Fn, LayerNormFn, MlpHalfFn, ModulateFn, _bn_act, layernorm)
+from .invpt_autograd import MultiScaleSumFn
+from .taskprompter_swin import _gather
 
 
 CHAN_KV_FN = True          # A/B switch: False = chan_kv through BLinearFn on a transposed copy of the pixel rows (rounds 2-5)
 WINATTN_BIAST = True       # A/B switch: the transposed bias table for the key-owner pass of the matrix-core window-attention backward (ABI 13)
 WINATTN_MFMA = True        # A/B switch: False = the exact fp32 VALU window-attention kernels on fp32 storage (rounds 2-5)
-
-
-def _gather(src, dst, idx, rows, C, ld_src, ld_dst, B, src_bs, dst_bs, skip_neg=0):
-    ops.call("gather_rows", src=src, dst=dst, idx=idx, rows=rows, C=C, ld_src=ld_src, ld_dst=ld_dst, src_dtype=dtype_code(src),
-             dst_dtype=dtype_code(dst), B=B, src_bs=src_bs, dst_bs=dst_bs, idx_bs=0, skip_neg=skip_neg)
 
 
 class WindowGatherFn(Function):
@@ -127,15 +132,9 @@ class WinAttnFn(Function):
     @staticmethod
     def forward(ctx, qkv, table, rel_index, mask, pix, geo, prec=None):
         B, nW, nH, T, ws2, N = geo
-        Nw, C = T + ws2, nH * 32
         bias = table.detach()[rel_index.view(-1)].view(ws2, ws2, nH).permute(2, 0, 1).contiguous().float()
-        out = torch.empty(B * nW * Nw, C, dtype=qkv.dtype, device=qkv.device)
-        rawlog = torch.zeros(B, nH, T, N, dtype=torch.float32, device=qkv.device)
-        kw = dict(qkv=qkv, out=out, bias=bias, mask=mask, pix=pix, nwin=B * nW, nW=nW, nH=nH, T=T, ws2=ws2, dtype=dtype_code(qkv),
-                  scale=32 ** -0.5, map_ld=N, map_off=T)
-        # fp32 storage (x3 / x3f): the forward's products as 3 bf16 MFMAs on split operands (fp32-class, like the x3 GEMMs); the backward of
-        # the x3f mode is the bf16 one (matrix cores), x3's the exact fp32 kernel
-        ops.call("winattn_fwd", rawmap=rawlog, mfma=1 if qkv.dtype == torch.float32 and WINATTN_MFMA else 0, **kw)
+        # fp32 storage: the backward of the x3f mode is the bf16 one (matrix cores), x3's the exact fp32 kernel
+        out, rawlog = sw.winattn_fwd(qkv, bias, mask, pix, geo, WINATTN_MFMA)
         # tensors go through save_for_backward — an OUTPUT kept on ctx directly is a reference cycle (node -> ctx -> out -> grad_fn = node) that
         # is never collected: the step leaked a block's qkv + out (GBs per step at the Swin-B shape) until round 6
         ctx.scalars = dict(nwin=B * nW, nW=nW, nH=nH, T=T, ws2=ws2, dtype=dtype_code(qkv), scale=32 ** -0.5, map_ld=N, map_off=T,
@@ -204,20 +203,9 @@ class ChanKvFn(Function):
 
     @staticmethod
     def forward(ctx, po, weight, bias, geo, prec, tag):
-        from ._lib import F32, OP_K, OP_R
-        from .taskprompter_swin import _split_k
-        B, N, T, C, HW = geo
-        ce2 = weight.shape[0]
+        C = geo[3]
         Wkv = ops.pack_linear([weight], prec, tag)                               # [1, 2ce, pitch(HW)]
-        Cp = ops.pitch(C)
-        pov = po.view(B, N, C)[:, T:]
-        Ks = _split_k(HW)
-        S = HW // Ks
-        slabs = torch.empty(B, S, ce2, Cp, dtype=torch.float32, device=po.device)
-        ops.call("gemm", A=Wkv, B=pov, D=slabs, M=ce2, N=C, K=Ks, a_op=OP_K, b_op=OP_R, a_dtype=dtype_code(Wkv), b_dtype=dtype_code(po), d_dtype=F32,
-                 prec=prec.code, lda=Wkv.shape[-1], ldb=C, ldd=Cp, batch=B * S, batch_inner=S, a_zo=0, a_zi=Ks, b_zo=N * C, b_zi=Ks * C,
-                 d_zo=S * ce2 * Cp, d_zi=ce2 * Cp, alpha=1.0, n_store=Cp)
-        kvT = slabs.sum(1) if S > 1 else slabs.view(B, ce2, Cp)
+        kvT = sw.chan_kv_gemm(po, Wkv, geo, prec)
         if bias is not None:
             kvT = kvT + bias.detach()[None, :, None]
         ctx.save_for_backward(po, Wkv)
@@ -226,7 +214,6 @@ class ChanKvFn(Function):
 
     @staticmethod
     def backward(ctx, dkv):
-        from ._lib import F32, OP_K, OP_R
         po, Wkv = ctx.saved_tensors
         (B, N, T, C, HW), prec, wshape, has_bias = ctx.meta
         prec = prec.bwd
@@ -306,15 +293,16 @@ def _inverse_merge_tables(res, T, device):
     return out
 
 
-def backbone_forward(model, img):
-    """Autograd twin of TaskPrompterSwin._forward_nograd -> [T, B*h0*w0, pitch(F)] task features."""
-    from . import taskprompter_swin as sw
+def backbone_forward(model, img, keep):
+    """TaskPrompterSwin's forward -> [T, B*h0*w0, pitch(F)] task features.  keep: somebody will differentiate it — blocks and patch mergings
+    then run as the autograd graph of this file, otherwise as the model's in-place `_block` / `_merge`."""
     p, prec = model.p, model.prec
     adt = prec.adt
     dev = img.device
     B = img.shape[0]
+    assert tuple(img.shape[-2:]) == model.full_img_size, "input size must equal img_size"
     img = img.float().contiguous()
-    if model.img_ds_ratio != 1:
+    if model.img_ds_ratio != 1:                                              # :666-667
         Hs, Ws = model.patch_embed.img_size
         small = torch.empty(B, 3, Hs, Ws, dtype=torch.float32, device=dev)
         ops.call("resize_nchw", args=[img, small, B * 3, img.shape[-2], img.shape[-1], Hs, Ws])
@@ -323,41 +311,50 @@ def backbone_forward(model, img):
     ps = model.patch_embed.patch_size[0]
     gh, gw = model.patch_grid
     C = model.embed_dim
+    N = T + gh * gw
+    # ---- patch embed (+ patch_norm) into the token buffer, prompts first ------------------------------------------------------------
     Kp = ops.pitch(3 * ps * ps)
     cols = torch.empty(B * gh * gw, Kp, dtype=adt, device=dev)
     ops.call("patchify", args=[img, cols, B, img.shape[-2], img.shape[-1], ps, Kp, dtype_code(cols)])
-    pe = _lin(model, cols, model.patch_embed.proj, 'swpe', torch.float32)
-    if isinstance(model.patch_embed.norm, torch.nn.LayerNorm):
-        nm = model.patch_embed.norm
-        pe = LayerNormFn.apply(pe.contiguous(), nm.weight, nm.bias, nm.eps, prec, torch.float32)
-    XT = torch.cat([model.task_prompts[None].expand(B, T, C), pe.reshape(B, gh * gw, C)], 1).reshape(B * (T + gh * gw), C)
-
+    nm = model.patch_embed.norm if isinstance(model.patch_embed.norm, torch.nn.LayerNorm) else None
+    if keep:
+        pe = _lin(model, cols, model.patch_embed.proj, 'pe', torch.float32)
+        if nm is not None:
+            pe = LayerNormFn.apply(pe.contiguous(), nm.weight, nm.bias, nm.eps, prec, torch.float32)
+        XT = torch.cat([model.task_prompts[None].expand(B, T, C), pe.reshape(B, gh * gw, C)], 1).reshape(B * N, C)
+    else:                                                                    # the GEMM writes the pixel rows of the token buffer itself
+        XT = torch.empty(B * N, C, dtype=torch.float32, device=dev)
+        pe = XT if nm is None else torch.zeros(B * N, C, dtype=torch.float32, device=dev)    # prompt rows: zeros (normalised, then overwritten)
+        model._lin(cols, model.patch_embed.proj, 'pe', out=pe.view(B, N, C)[:, T:], d_rows=(gh * gw, N * C, C), M=B * gh * gw)
+        if nm is not None:
+            ops.call("layernorm_fwd", x=pe, y=XT, gamma=nm.weight.detach(), beta=nm.bias.detach(), mean=None, rstd=None, rows=B * N, C=C,
+                     ldx=C, ldy=C, y_dtype=F32, eps=nm.eps)
+        XT.view(B, N, C)[:, :T] = model.task_prompts.detach()
+    block, merge = (partial(_block, model), partial(_merge, model)) if keep else (model._block, model._merge)
     fea_levels = []
     rawlog = rawchan = None
-    nl = model.num_layers
     for il, layer in enumerate(model.layers):
         res = layer.input_resolution
+        nH = layer.blocks[0].num_heads
         for ib, blk in enumerate(layer.blocks):
-            XT, rawlog, rawchan = _block(model, blk, (il, ib), XT, B, T, res)
+            XT, rawlog, rawchan = block(blk, (il, ib), XT, B, T, res)
         if layer.downsample is not None:
-            XT, rawlog, rawchan = _merge(model, layer.downsample, il, XT, rawlog, rawchan, B, T, res, layer.blocks[0].num_heads)
-            r2 = (res[0] // 2, res[1] // 2)
-            fea_levels.append(_task_features(model, XT, rawlog, rawchan, il, B, r2, 2 * layer.dim, 2 * layer.dim // layer.blocks[0].num_heads))
-    res = model.layers[-1].input_resolution
-    Cl = model.layers[-1].dim
-    xf = LayerNormFn.apply(XT, model.norm.weight, model.norm.bias, model.norm.eps, prec, torch.float32)
-    fea_levels.append(_task_features(model, xf, rawlog, rawchan, nl - 1, B, res, Cl, Cl // model.layers[-1].blocks[0].num_heads))
+            XT, rawlog, rawchan = merge(layer.downsample, il, XT, rawlog, rawchan, B, T, res, nH)
+            fea_levels.append(_task_features(model, XT, rawlog, rawchan, il, B, (res[0] // 2, res[1] // 2), 2 * layer.dim, 2 * layer.dim // nH, keep))
+    last = model.layers[-1]
+    xf = layernorm(XT, model.norm.weight, model.norm.bias, model.norm.eps, prec, torch.float32, keep)
+    fea_levels.append(_task_features(model, xf, rawlog, rawchan, model.num_layers - 1, B, last.input_resolution, last.dim,
+                                     last.dim // last.blocks[0].num_heads, keep))
+    # multi-scale fusion (:699-709): every level resized to the first one's grid and summed as ONE node (inside the kernel), then a 3x3 conv
     h0, w0 = model.feature_hw
     Fp = fea_levels[0].shape[-1]
-    # every level resized to the finest one and summed as ONE node (the resizes accumulate into the fp32 sum inside the kernel; a level that
-    # already has the target size is added / differentiated as the identity): no [T, B*h0*w0, Fp] tensor per level, no add passes
-    from .invpt_autograd import MultiScaleSumFn
     sizes = [(2 * model.resolution[i][0], 2 * model.resolution[i][1]) for i in range(len(fea_levels))]
     acc = MultiScaleSumFn.apply((B, Fp, h0, w0, sizes), *[f.contiguous() for f in fea_levels])
+    if adt != torch.float32:
+        acc = acc.to(adt) if keep else ops.cast2d(acc.view(-1, Fp), acc.shape[0] * acc.shape[1], Fp, Fp, adt, ldd=Fp).view(acc.shape[0], -1, Fp)
     names = list(model.all_tasks)
     F = p.final_embed_dim
-    accq = acc if adt == torch.float32 else acc.to(adt)
-    return Conv3x3Fn.apply(accq, (B, h0, w0, F, F), prec, 'swmsf', *[model.multi_scale_fuse[t].weight for t in names],
+    return Conv3x3Fn.apply(acc, (B, h0, w0, F, F), prec, 'msf', *[model.multi_scale_fuse[t].weight for t in names],
                            *[model.multi_scale_fuse[t].bias for t in names])
 
 
@@ -376,7 +373,6 @@ def _drop_scales(model, blk, tag, B, device):
 
 
 def _block(model, blk, tag, XT, B, T, res):
-    from . import taskprompter_swin as sw
     drops = _drop_scales(model, blk, tag, B, XT.device)
     prec = model.prec
     adt = prec.adt
@@ -387,7 +383,7 @@ def _block(model, blk, tag, XT, B, T, res):
     N, ws2 = T + H * W, ws * ws
     Nw, nW = T + ws2, (Hp // ws) * (Wp // ws)
     part, pix, rev = sw.window_tables(res, ws, shift, Hp, Wp, T, dev)
-    tag = ('swt',) + tag
+    tag = ('sw',) + tag
     a = blk.attn
     xn = LayerNormFn.apply(XT, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, prec, None)
     prompts = XT.view(B, N, C)[:, :T].reshape(B * T, C)
@@ -423,14 +419,13 @@ def _block(model, blk, tag, XT, B, T, res):
 
 
 def _merge(model, ds, il, XT, rawlog, rawchan, B, T, res, nH):
-    from . import taskprompter_swin as sw
     prec = model.prec
     adt = prec.adt
     dev = XT.device
     H, W = res
     C = ds.dim
     N, N2 = T + H * W, T + (H // 2) * (W // 2)
-    tag = ('swtm', il)
+    tag = ('swm', il)
     cat = MergeGatherFn.apply(XT, sw.merge_tables(res, T, dev), _inverse_merge_tables(res, T, dev), (B, N, N2, T, C))
     catn = LayerNormFn.apply(cat, ds.norm.weight, ds.norm.bias, ds.norm.eps, prec, None)
     red = _lin(model, catn, ds.reduction, tag + ('red',), torch.float32)                              # [B*(N2-T), 2C]
@@ -443,7 +438,9 @@ def _merge(model, ds, il, XT, rawlog, rawchan, B, T, res, nH):
     return XT2.contiguous(), raw2, rc2.reshape(B, T, nwin2, 2 * C).contiguous()
 
 
-def _task_features(model, xsrc, rawlog, rawchan, il, B, res, C, hg):
+def _task_features(model, xsrc, rawlog, rawchan, il, B, res, C, hg, keep):
+    """cal_task_feature (taskprompter_swin.py:715-777) of one level, all tasks -> [T, B*2h*2w, pitch(F)] activation dtype.  One statement for
+    both paths, except that a forward in eval mode that nobody differentiates folds the BatchNorm into the first 3x3 conv's epilogue."""
     p, prec = model.p, model.prec
     names = list(model.all_tasks)
     T = len(names)
@@ -459,14 +456,20 @@ def _task_features(model, xsrc, rawlog, rawchan, il, B, res, C, hg):
     for t in names:
         dec_w += [model.fea_decode_spa[il][t][0].weight, model.fea_decode_chan[il][t][0].weight]
         dec_b += [model.fea_decode_spa[il][t][0].bias, model.fea_decode_chan[il][t][0].bias]
-    cat = BLinearFn.apply(mod, tar, 'catpair', None, "split" if sp else None, prec, ('swtdec', il), mod_lo, *dec_w, *dec_b)
+    cat = BLinearFn.apply(mod, tar, 'catpair', None, "split" if sp else None, prec, ('swdec', il), mod_lo, *dec_w, *dec_b)
     cat, cat_lo = cat if sp else (cat, None)
     del mod, mod_lo
     ff = [model.fea_fuse[il][t] for t in names]
     kmap = (2 * tarp, [(0, 0, tar), (tarp, tar, tar)])
-    y0 = BLinearFn.apply(cat, F, 'plain', kmap, None, prec, ('swtf0', il), cat_lo, *[m[0].weight for m in ff], *[m[0].bias for m in ff])
+    y0 = BLinearFn.apply(cat, F, 'plain', kmap, None, prec, ('swf0', il), cat_lo, *[m[0].weight for m in ff], *[m[0].bias for m in ff])
     del cat, cat_lo
-    y0 = BilinearFn.apply(y0, (B, y0.shape[-1], h, w, 2 * h, 2 * w), prec.adt, False)
-    y1 = Conv3x3Fn.apply(y0, (B, 2 * h, 2 * w, F, F), prec, ('swtf1', il), *[m[1].weight for m in ff], *[m[1].bias for m in ff])
-    y1 = _bn_act(y1, [m[2] for m in ff], F, ACT_GELU, model.training)
-    return Conv3x3Fn.apply(y1, (B, 2 * h, 2 * w, F, F), prec, ('swtf4', il), *[m[4].weight for m in ff], *[m[4].bias for m in ff])
+    y0 = BilinearFn.apply(y0, (B, y0.shape[-1], h, w, 2 * h, 2 * w), prec.adt, False)        # :737 / :765
+    geo = (B, 2 * h, 2 * w, F, F)
+    bns = [m[2] for m in ff]
+    if keep or model.training:
+        y1 = Conv3x3Fn.apply(y0, geo, prec, ('swf1', il), *[m[1].weight for m in ff], *[m[1].bias for m in ff])
+        y1 = _bn_act(y1, bns, F, ACT_GELU, model.training)
+    else:
+        sc, sh = bn_mod.fold(bns, [m[1].bias for m in ff], ('swf2', il))
+        y1 = ops.conv3x3(y0, ops.pack_conv3([m[1].weight for m in ff], prec, ('swf1', il)), F, F, *geo[:3], prec, bias=sh, colscale=sc, act=ACT_GELU)
+    return Conv3x3Fn.apply(y1, geo, prec, ('swf4', il), *[m[4].weight for m in ff], *[m[4].bias for m in ff])

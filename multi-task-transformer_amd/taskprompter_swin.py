@@ -2,9 +2,9 @@
 reference's constructor arguments and state_dict layout (so `load_state_dict(strict=True)` takes its checkpoints and the module drops
 into TaskPrompterWrapper / get_model), executed as a fused schedule on libmtt_hip.so.
 
-Status: the forward (inference) path below is the fused one; with gradients enabled `forward_nhwc` builds the autograd graph of
-swin_autograd.py (first, unoptimised training path: HIP kernels for the heavy operators, torch glue for residual adds and row
-concatenations, DropPath 0 only).
+The forward itself — level loop, task features, multi-scale fusion — is swin_autograd.backbone_forward, for inference and training alike.
+Only the block and the patch merging are two schedules: the in-place ones below (`_block`, `_merge`: the residual stream updated in
+place, GEMM outputs written into row ranges) when nobody differentiates, the autograd nodes of swin_autograd.py otherwise.
 
 Schedule of a SwinTransformerBlock (taskprompter_swin.py:324-414), per image a token buffer XT [T + H*W, C] fp32 with the T task
 prompts first (like the ViT variant):
@@ -24,8 +24,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import bn as bn_mod
-from . import ops
+from . import autograd_path, ops
 from ._lib import ACT_GELU, F32, OP_K, OP_R, dtype_code
 from .taskprompter import BatchNorm2d, Mlp, _init_vit_weights, _prec_of, trunc_normal_
 
@@ -107,9 +106,35 @@ def merge_tables(res, T, device):
     return out
 
 
-def _gather(src, dst, idx, rows, C, ld_src, ld_dst, B, src_bs, dst_bs):
+def _gather(src, dst, idx, rows, C, ld_src, ld_dst, B, src_bs, dst_bs, skip_neg=0):
     ops.call("gather_rows", src=src, dst=dst, idx=idx, rows=rows, C=C, ld_src=ld_src, ld_dst=ld_dst, src_dtype=dtype_code(src),
-             dst_dtype=dtype_code(dst), B=B, src_bs=src_bs, dst_bs=dst_bs, idx_bs=0)
+             dst_dtype=dtype_code(dst), B=B, src_bs=src_bs, dst_bs=dst_bs, idx_bs=0, skip_neg=skip_neg)
+
+
+def winattn_fwd(qkv, bias, mask, pix, geo, mfma=True):
+    """window tokens' qkv [B*nW*(T + ws2), 3C] -> (out [B*nW*(T + ws2), C], raw prompt logits [B, nH, T, N] fp32 in image layout).  fp32
+    storage (x3 / x3f): the products as 3 bf16 MFMAs on split operands (fp32-class) unless mfma=False (the exact fp32 VALU kernel)."""
+    B, nW, nH, T, ws2, N = geo
+    out = torch.empty(B * nW * (T + ws2), nH * 32, dtype=qkv.dtype, device=qkv.device)
+    rawlog = torch.zeros(B, nH, T, N, dtype=torch.float32, device=qkv.device)
+    ops.call("winattn_fwd", qkv=qkv, out=out, rawmap=rawlog, bias=bias, mask=mask, pix=pix, nwin=B * nW, nW=nW, nH=nH, T=T, ws2=ws2,
+             dtype=dtype_code(qkv), scale=32 ** -0.5, map_ld=N, map_off=T, mfma=1 if mfma and qkv.dtype == torch.float32 else 0)
+    return out, rawlog
+
+
+def chan_kv_gemm(po, Wkv, geo, prec):
+    """kvT[b] = W_kv [2ce, HW] x x_attn[b] [HW, C] (taskprompter_swin.py:393-397, bias apart) -> [B, 2ce, pitch(C)] fp32.  po [B*N, C]: the
+    attention branch in token order, read in place — the pixels are the reduction axis (73 728 at the first Swin-B stage) and M x N is
+    tiny, so K is split over workgroups and the fp32 slabs are summed."""
+    B, N, T, C, K = geo
+    ce2, Cp = Wkv.shape[1], ops.pitch(C)
+    Ks = _split_k(K)
+    S = K // Ks
+    slabs = torch.empty(B, S, ce2, Cp, dtype=torch.float32, device=po.device)
+    ops.call("gemm", A=Wkv, B=po.view(B, N, C)[:, T:], D=slabs, M=ce2, N=C, K=Ks, a_op=OP_K, b_op=OP_R, a_dtype=dtype_code(Wkv),
+             b_dtype=dtype_code(po), d_dtype=F32, prec=prec.code, lda=Wkv.shape[-1], ldb=C, ldd=Cp, batch=B * S, batch_inner=S, a_zo=0, a_zi=Ks,
+             b_zo=N * C, b_zi=Ks * C, d_zo=S * ce2 * Cp, d_zi=ce2 * Cp, alpha=1.0, n_store=Cp)
+    return slabs.sum(1) if S > 1 else slabs.view(B, ce2, Cp)
 
 
 # ---- parameter holders with the reference's names -----------------------------------------------------------------------------------
@@ -255,10 +280,9 @@ class TaskPrompterSwin(nn.Module):
         raise RuntimeError("the Swin backbone returns its features at their final resolution")
 
     def forward_nhwc(self, img, upsample=True):
-        if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
-            from . import swin_autograd
-            return swin_autograd.backbone_forward(self, img)
-        return self._forward_nograd(img)
+        from . import swin_autograd
+        keep = torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters())
+        return swin_autograd.backbone_forward(self, img, keep)
 
     # ---- forward ---------------------------------------------------------------------------------------------------------------------
     def _decoder_split(self, C):
@@ -266,81 +290,15 @@ class TaskPrompterSwin(nn.Module):
         hi / lo planes) — whole 32-deep K steps over the level's C channels and over the padded concatenation (TaskPrompter._decoder_split)."""
         return self.prec.split and ops.split_gemm_ok(C) and ops.split_gemm_ok(2 * ops.pitch(self.p.level_embed_dim))
 
-    SPLIT_MIN_ROWS = 2048
-
-    def _lin(self, x, layer, tag, **kw):
+    def _lin(self, x, layer, tag, planes=True, **kw):
         """x @ layer.weight^T (+ bias) through mtt_gemm; kw as ops.linear.  x3f: a large fp32 operand is split into hi / lo planes by one
-        pass and the product runs on the split-plane LDS-DMA kernel (pre-split weight planes) instead of the register-staged x3 one."""
+        pass and the product runs on the split-plane LDS-DMA kernel (pre-split weight planes) instead of the register-staged x3 one
+        (BLinearFn's rule and row threshold; planes=False: never)."""
         N, K = layer.weight.shape[0], layer.weight.shape[1]
         bias = layer.bias.detach()[None] if layer.bias is not None else None
-        split = (self.prec.split and torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() and x.shape[1] == K
-                 and kw.get("a_rows") is None and x.shape[0] >= self.SPLIT_MIN_ROWS and ops.split_gemm_ok(K))
+        split = (planes and self.prec.split and torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() and x.shape[1] == K
+                 and kw.get("a_rows") is None and x.shape[0] >= autograd_path.AUTO_SPLIT_MIN_ROWS and ops.split_gemm_ok(K))
         return ops.linear(ops.split_cast(x) if split else x, ops.pack_linear([layer.weight], self.prec, tag, split=split), N, self.prec, bias=bias, **kw)
-
-    def _forward_nograd(self, img):
-        p, prec = self.p, self.prec
-        dev = img.device
-        B = img.shape[0]
-        assert tuple(img.shape[-2:]) == self.full_img_size, "input size must equal img_size"
-        img = img.float().contiguous()
-        if self.img_ds_ratio != 1:                                          # :666-667
-            Hs, Ws = self.patch_embed.img_size
-            small = torch.empty(B, 3, Hs, Ws, dtype=torch.float32, device=dev)
-            ops.call("resize_nchw", args=[img, small, B * 3, img.shape[-2], img.shape[-1], Hs, Ws])
-            img = small
-        T = self.prompts_len
-        ps = self.patch_embed.patch_size[0]
-        gh, gw = self.patch_grid
-        C = self.embed_dim
-        N = T + gh * gw
-        # ---- patch embed (+ patch_norm) into the token buffer, prompts first -------------------------------------------------------
-        Kp = ops.pitch(3 * ps * ps)
-        cols = torch.empty(B * gh * gw, Kp, dtype=prec.adt, device=dev)
-        ops.call("patchify", args=[img, cols, B, img.shape[-2], img.shape[-1], ps, Kp, dtype_code(cols)])
-        XT = torch.empty(B * N, C, dtype=torch.float32, device=dev)
-        if isinstance(self.patch_embed.norm, nn.LayerNorm):
-            pe = torch.zeros(B * N, C, dtype=torch.float32, device=dev)         # prompt rows: zeros (normalised, then overwritten)
-            self._lin(cols, self.patch_embed.proj, 'pe', out=pe.view(B, N, C)[:, T:], d_rows=(gh * gw, N * C, C), M=B * gh * gw)
-            ops.call("layernorm_fwd", x=pe, y=XT, gamma=self.patch_embed.norm.weight.detach(), beta=self.patch_embed.norm.bias.detach(),
-                     mean=None, rstd=None, rows=B * N, C=C, ldx=C, ldy=C, y_dtype=F32, eps=self.patch_embed.norm.eps)
-        else:
-            self._lin(cols, self.patch_embed.proj, 'pe', out=XT.view(B, N, C)[:, T:], d_rows=(gh * gw, N * C, C), M=B * gh * gw)
-        XT.view(B, N, C)[:, :T] = self.task_prompts.detach()
-
-        fea_levels = []
-        rawlog = rawchan = None
-        nl = self.num_layers
-        for il, layer in enumerate(self.layers):
-            res = layer.input_resolution
-            for ib, blk in enumerate(layer.blocks):
-                XT, rawlog, rawchan = self._block(blk, (il, ib), XT, B, T, res)
-            if layer.downsample is not None:
-                XT, rawlog, rawchan = self._merge(layer.downsample, il, XT, rawlog, rawchan, B, T, res, layer.blocks[0].num_heads)
-                C2 = 2 * layer.dim
-                r2 = (res[0] // 2, res[1] // 2)
-                fea_levels.append(self._task_features(XT, XT.view(B, T + r2[0] * r2[1], C2)[:, T:], rawlog, rawchan, il, B, r2, C2,
-                                                      C2 // layer.blocks[0].num_heads))
-        res = self.layers[-1].input_resolution
-        Cl = self.layers[-1].dim
-        xf, _, _ = ops.layernorm(XT, self.norm.weight.detach(), self.norm.bias.detach(), self.norm.eps, prec, out_dtype=torch.float32)
-        Nl = T + res[0] * res[1]
-        fea_levels.append(self._task_features(xf, xf.view(B, Nl, Cl)[:, T:], rawlog, rawchan, nl - 1, B, res, Cl,
-                                              Cl // self.layers[-1].blocks[0].num_heads))
-        # ---- multi-scale fusion (:699-709): every level resized to the first one's grid and summed, then a 3x3 conv ----------------
-        h0, w0 = self.feature_hw
-        Fp = fea_levels[0].shape[-1]
-        Tn = len(self.all_tasks)
-        acc = torch.empty(Tn, B * h0 * w0, Fp, dtype=torch.float32, device=dev)
-        for i, f in enumerate(fea_levels):
-            hi, wi = 2 * self.resolution[i][0], 2 * self.resolution[i][1]
-            ops.call("bilinear_fwd", **{"in": f}, out=acc, B=Tn * B, C=Fp, Hin=hi, Win=wi, Hout=h0, Wout=w0, ld_in=Fp, ld_out=Fp,
-                     in_dtype=dtype_code(f), out_dtype=F32, out_nchw=0, accumulate=1 if i else 0)
-        F = p.final_embed_dim
-        names = [t for t in self.all_tasks]
-        Wm = ops.pack_conv3([self.multi_scale_fuse[t].weight for t in names], prec, 'msf')
-        bm = ops.stack_vec([self.multi_scale_fuse[t].bias for t in names], 'msfb')
-        accq = acc if prec.adt == torch.float32 else ops.cast2d(acc.view(-1, Fp), Tn * B * h0 * w0, Fp, Fp, prec.adt, ldd=Fp).view(Tn, -1, Fp)
-        return ops.conv3x3(accq, Wm, F, F, B, h0, w0, prec, bias=bm)
 
     def _block(self, blk, tag, XT, B, T, res):
         prec = self.prec
@@ -363,10 +321,7 @@ class TaskPrompterSwin(nn.Module):
         bias = ops._cached((tag, 'rpb'), [a.relative_position_bias_table],
                            lambda: a.relative_position_bias_table.detach()[a.relative_position_index.view(-1)]
                            .view(ws2, ws2, nH).permute(2, 0, 1).contiguous().float())
-        ao = torch.empty(B * nW * Nw, C, dtype=prec.adt, device=dev)
-        rawlog = torch.zeros(B, nH, T, N, dtype=torch.float32, device=dev)
-        ops.call("winattn_fwd", qkv=qkv, out=ao, rawmap=rawlog, bias=bias, mask=blk.attn_mask, pix=pix, nwin=B * nW, nW=nW, nH=nH, T=T,
-                 ws2=ws2, dtype=dtype_code(qkv), scale=32 ** -0.5, map_ld=N, map_off=T, mfma=1 if qkv.dtype == torch.float32 else 0)
+        ao, rawlog = winattn_fwd(qkv, bias, blk.attn_mask, pix, (B, nW, nH, T, ws2, N))
         # back to image order; prompt rows = mean over the windows (:208; the mean commutes with proj)
         ao_img = torch.empty(B * N, C, dtype=prec.adt, device=dev)
         _gather(ao, ao_img.view(B, N, C)[:, T:], rev, H * W, C, C, C, B, nW * Nw * C, N * C)
@@ -380,15 +335,7 @@ class TaskPrompterSwin(nn.Module):
         q = self._lin(chan_p, blk.chan_q, tag + ('cq',), out_dtype=torch.float32)[0]                     # [B*T, ce]
         Wkv = ops.pack_linear([blk.chan_kv.weight], prec, tag + ('ckv',))                                # [1, 2ce, pitch(HW)]
         Cp = ops.pitch(C)
-        pov = po.view(B, N, C)[:, T:]
-        K = H * W
-        Ks = _split_k(K)                                                        # the reduction axis is the pixel count (73 728 at the first
-        S = K // Ks                                                             # Swin-B stage) and M x N is tiny: split it over workgroups
-        slabs = torch.empty(B, S, 2 * ce, Cp, dtype=torch.float32, device=dev)
-        ops.call("gemm", A=Wkv, B=pov, D=slabs, M=2 * ce, N=C, K=Ks, a_op=OP_K, b_op=OP_R, a_dtype=dtype_code(Wkv), b_dtype=dtype_code(po),
-                 d_dtype=F32, prec=prec.code, lda=Wkv.shape[-1], ldb=C, ldd=Cp, batch=B * S, batch_inner=S, a_zo=0, a_zi=Ks, b_zo=N * C,
-                 b_zi=Ks * C, d_zo=S * 2 * ce * Cp, d_zi=2 * ce * Cp, alpha=1.0, n_store=Cp)
-        kvT = slabs.sum(1) if S > 1 else slabs.view(B, 2 * ce, Cp)
+        kvT = chan_kv_gemm(po, Wkv, (B, N, T, C, H * W), prec)
         rawchan = torch.empty(B, T, nwin * nwin, C, dtype=torch.float32, device=dev)
         cx = torch.empty(B * T, ce, dtype=torch.float32, device=dev)
         ops.call("chanattn_fwd", q=q, kvT=kvT, rawchan=rawchan, cx=cx, B=B, T=T, C=C, ce=ce, nh=nwin, nw=nwin, kv_dtype=F32, ldk=Cp,
@@ -400,7 +347,8 @@ class TaskPrompterSwin(nn.Module):
         # MLP over prompts + pixels (:413, :409)
         xn2, _, _ = ops.layernorm(XT2, blk.norm2.weight.detach(), blk.norm2.bias.detach(), blk.norm2.eps, prec)
         hmid = self._lin(xn2, blk.mlp.fc1, tag + ('fc1',), act=ACT_GELU)[0]
-        self._lin(hmid, blk.mlp.fc2, tag + ('fc2',), out=XT2, resid=XT2)
+        # fc2 on planes only where fc1's K allows them too (mlp_half's rule: a one-head stage registers no second, pre-split fc2 pack)
+        self._lin(hmid, blk.mlp.fc2, tag + ('fc2',), planes=ops.split_gemm_ok(C), out=XT2, resid=XT2)
         return XT2, rawlog, rawchan
 
     def _merge(self, ds, il, XT, rawlog, rawchan, B, T, res, nH):
@@ -424,57 +372,6 @@ class TaskPrompterSwin(nn.Module):
         nwin2 = rawchan.shape[2]
         rc2 = self._lin(rawchan.view(B * T * nwin2, C), ds.process_chan_attn, tag + ('pca',), out_dtype=torch.float32)[0]
         return XT2, raw2, rc2.view(B, T, nwin2, -1)[..., :2 * C].contiguous()
-
-    def _task_features(self, xsrc, xview, rawlog, rawchan, il, B, res, C, hg):
-        """cal_task_feature (taskprompter_swin.py:715-777) for all tasks -> [T, B*2h*2w, pitch(F)] activation dtype."""
-        p, prec = self.p, self.prec
-        names = self.all_tasks
-        T = len(names)
-        h, w = res
-        hw, N = h * w, T + h * w
-        tar, F = p.level_embed_dim, p.final_embed_dim
-        tarp = ops.pitch(tar)
-        nwin = int(math.isqrt(p.chan_nheads))
-        sp = self._decoder_split(C)
-        mod = ops.modulate(xview, C, N * C, rawlog, rawchan, B, T, N, C, (h, w), (nwin, nwin), prec, hg=hg, split=sp)
-        dec_w, dec_b = [], []
-        for t in names:
-            dec_w += [self.fea_decode_spa[il][t][0].weight, self.fea_decode_chan[il][t][0].weight]
-            dec_b += [self.fea_decode_spa[il][t][0].bias, self.fea_decode_chan[il][t][0].bias]
-        Wdec = ops.pack_linear(dec_w, prec, ('swdec', il), split=sp)
-        bdec = ops.stack_vec(dec_b, ('swdecb', il))
-        cat = ops.Split.empty((T, B * hw, 2 * tarp), xsrc.device) if sp else torch.empty(T, B * hw, 2 * tarp, dtype=prec.adt, device=xsrc.device)
-        ops.linear(mod, Wdec, tar, prec, bias=bdec, out=cat, batch_inner=2, d_z=(B * hw * 2 * tarp, tarp), ldd=2 * tarp, n_store=tarp)
-        del mod
-        f0 = [self.fea_fuse[il][t][0].weight for t in names]
-
-        def build_f0():
-            with torch.no_grad():
-                buf = torch.zeros(T, F, 2 * tarp, dtype=torch.float32, device=f0[0].device)
-                for i, wt in enumerate(f0):
-                    w2 = wt.detach().reshape(F, 2 * tar)
-                    buf[i, :, :tar] = w2[:, :tar]
-                    buf[i, :, tarp:tarp + tar] = w2[:, tar:]
-                return buf.to(prec.adt)
-        if sp:
-            W0 = ops.pack_kmap(f0, F, 2 * tarp, [(0, 0, tar), (tarp, tar, tar)], prec, ('swf0', il), split=True)
-        else:
-            W0 = ops._cached(('swf0', il, prec.name, tuple(id(q) for q in f0)), f0, build_f0)
-        b0 = ops.stack_vec([self.fea_fuse[il][t][0].bias for t in names], ('swf0b', il))
-        y0 = ops.linear(cat, W0, F, prec, bias=b0, out_dtype=torch.float32 if sp else None)   # 1x1s before the resize: they commute with it
-        del cat
-        y0 = ops.bilinear(y0, B, y0.shape[-1], h, w, 2 * h, 2 * w, prec.adt)        # :737 / :765
-        ff = [self.fea_fuse[il][t] for t in names]
-        Wc = ops.pack_conv3([m[1].weight for m in ff], prec, ('swf1', il))
-        bns = [m[2] for m in ff]
-        if self.training:
-            y1 = ops.conv3x3(y0, Wc, F, F, B, 2 * h, 2 * w, prec, bias=ops.stack_vec([m[1].bias for m in ff], ('swf1b', il)))
-            y1 = bn_mod.train_forward(y1, F, list(bns), ACT_GELU)[0]
-        else:
-            sc, sh = bn_mod.fold(bns, [m[1].bias for m in ff], ('swf2', il))
-            y1 = ops.conv3x3(y0, Wc, F, F, B, 2 * h, 2 * w, prec, bias=sh, colscale=sc, act=ACT_GELU)
-        W4 = ops.pack_conv3([m[4].weight for m in ff], prec, ('swf4', il))
-        return ops.conv3x3(y1, W4, F, F, B, 2 * h, 2 * w, prec, bias=ops.stack_vec([m[4].bias for m in ff], ('swf4b', il)))
 
 
 def _split_k(K, target=1152):

@@ -78,7 +78,6 @@ def test_gradients_match_the_emulator(leg, monkeypatch):
         # the switches of test_host_cpu.check_swin_x3f_split_planes: the miniature takes Swin-B's split-plane stage Linears / task features
         # and the matrix-core window attention (mtt_winattn_desc.mfma)
         monkeypatch.setattr(mtt_amd.autograd_path, "AUTO_SPLIT_MIN_ROWS", 64)
-        monkeypatch.setattr(mtt_amd.taskprompter_swin.TaskPrompterSwin, "SPLIT_MIN_ROWS", 64)
         key = ("split_min_rows", 64)
     r = train_check.device_vs_emulator(family, name, mode, "cuda:0", gemm_variant=variant, pitch32_from=pitch, tasks=tasks, call=call, key=key)
     rel = sorted(train_check.rel_errors({k: v for k, v in r.errs.items()

@@ -313,6 +313,35 @@ def test_swin_x3f_split_planes_and_matrix_core_window_attention(name, monkeypatc
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("name,prec", [("mini_swin_sp", "x3f"), ("mini_swin_pad", "bf16")])
+def test_swin_level_features_do_not_depend_on_keep(name, prec, monkeypatch):
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from test_host_cpu import check_swin_level_features_do_not_depend_on_keep
+    check_swin_level_features_do_not_depend_on_keep(name, prec, "cuda", monkeypatch)
+
+
+@pytest.mark.gpu
+def test_swin_eval_pass_registers_no_second_pack_set():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import mtt_amd
+    from test_host_cpu import check_swin_eval_pass_registers_no_second_pack_set
+    try:
+        check_swin_eval_pass_registers_no_second_pack_set("cuda")
+    finally:
+        mtt_amd.ops.clear_pack_cache()
+
+
+@pytest.mark.gpu
+def test_swin_training_path_checks_its_input_size():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from test_host_cpu import check_swin_training_path_checks_its_input_size
+    check_swin_training_path_checks_its_input_size("cuda")
+
+
+@pytest.mark.gpu
 @pytest.mark.timeout(1500)
 def test_mixed_precision_training_trajectory_follows_the_fp32_reference_over_200_steps():
     """Does x3f TRAIN like the reference?  The reference trains in fp32 (no AMP); x3f = fp32-class forward + bf16

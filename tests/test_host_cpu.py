@@ -806,7 +806,6 @@ def check_swin_x3f_split_planes(name, device, monkeypatch):
     import train_check
     from oracle import swin_oracle as swo
     monkeypatch.setattr(mtt_amd.autograd_path, "AUTO_SPLIT_MIN_ROWS", 64)
-    monkeypatch.setattr(mtt_amd.taskprompter_swin.TaskPrompterSwin, "SPLIT_MIN_ROWS", 64)
     seen = []
     inner = mtt_amd.ops.call
     monkeypatch.setattr(mtt_amd.ops, "call", lambda n, **kw: (seen.append((n, kw.get("a_dtype"), kw.get("mfma"), kw.get("out_lo") is not None)), inner(n, **kw))[1])
@@ -841,6 +840,111 @@ def check_swin_x3f_split_planes(name, device, monkeypatch):
 @pytest.mark.parametrize("name", ["mini_swin_sp", "mini_swin"])
 def test_swin_x3f_split_planes_on_emulator(emulated, monkeypatch, name):
     check_swin_x3f_split_planes(name, "cpu", monkeypatch)
+
+
+def _swin_product(name, prec, device):
+    """-> (cfg, TaskPrompterWrapper on `device` with the synthetic weights, a batch of two images)"""
+    cfg = configs.swin(name)
+    model = conftest.build_product_model(cfg, prec, device)
+    contract = [(k, list(v.shape)) for k, v in model.state_dict().items() if k.rsplit(".", 1)[-1] not in weights.DERIVED_BUFFERS]
+    model.load_state_dict({k: v.to(device) for k, v in weights.synth_state_dict(contract, 0).items()}, strict=False)
+    return cfg, model, weights.synth_images(2, cfg["img_size"], 1).to(device)
+
+
+def _launch_fields(v):
+    """a launch argument without its tensors: what two statements of one schedule must agree on"""
+    if torch.is_tensor(v):
+        return "tensor"
+    if isinstance(v, dict):
+        return {k: _launch_fields(q) for k, q in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_launch_fields(q) for q in v]
+    return v
+
+
+def check_swin_level_features_do_not_depend_on_keep(name, prec, device, monkeypatch):
+    """(shared with tests/test_gpu_train.py) swin_autograd._task_features is ONE statement: in train mode, on the arguments of a real
+    forward, the autograd graph (keep=True, gradients recorded) and the plain forward (keep=False under no_grad) give bitwise equal
+    features at all four levels from the same launches.  mini_swin_sp x3f with the row threshold of the split pass lowered: planes through
+    modulate, catpair and kmap; mini_swin_pad bf16: ragged widths 16 and 24, the one-tensor kmap pack, 3 tasks."""
+    import importlib
+    import mtt_amd
+    sa = importlib.import_module(mtt_amd.__name__ + ".swin_autograd")
+    if name == "mini_swin_sp":
+        monkeypatch.setattr(mtt_amd.autograd_path, "AUTO_SPLIT_MIN_ROWS", 64)
+    cfg, model, x = _swin_product(name, prec, device)
+    model.train()
+    levels = []
+    real = sa._task_features
+    monkeypatch.setattr(sa, "_task_features", lambda *a: (levels.append(a), real(*a))[1])
+    with torch.no_grad():
+        model.backbone.forward_nhwc(x)
+    monkeypatch.setattr(sa, "_task_features", real)
+    assert len(levels) == 4 and all(a[-1] is False for a in levels)
+    seen = []
+    inner = mtt_amd.ops.call
+    monkeypatch.setattr(mtt_amd.ops, "call", lambda n, **kw: (seen.append((n, _launch_fields(kw))), inner(n, **kw))[1])
+    for a in levels:
+        got = {}
+        for keep in (True, False):
+            mtt_amd.ops.clear_pack_cache()
+            del seen[:]
+            with torch.set_grad_enabled(keep):
+                y = real(*a[:-1], keep)
+            assert y.requires_grad == keep
+            got[keep] = (y.detach(), list(seen))
+        assert torch.equal(got[True][0], got[False][0]), (name, a[4])
+        assert got[True][1] == got[False][1], (name, a[4])
+        assert [n for n, _ in got[True][1]].count("gemm") >= 4 and any(n == "modulate" for n, _ in got[True][1])
+
+
+@pytest.mark.parametrize("name,prec", [("mini_swin_sp", "x3f"), ("mini_swin_pad", "bf16")])
+def test_swin_level_features_do_not_depend_on_keep(emulated, monkeypatch, name, prec):
+    check_swin_level_features_do_not_depend_on_keep(name, prec, "cpu", monkeypatch)
+
+
+def check_swin_eval_pass_registers_no_second_pack_set(device):
+    """(shared with tests/test_gpu_train.py) Both Swin paths take their weight packs under the same tags and through the same pack calls:
+    an evaluation pass in front of a training step leaves exactly the registry entries the training step alone leaves (ops._refresh_packs
+    re-copies EVERY registered pack after an optimizer step, so a second set would be re-packed on every later step)."""
+    import mtt_amd
+    cfg, model, x = _swin_product("mini_swin", "x3f", device)
+    bb = model.backbone
+
+    def train_pass():
+        model.train()
+        y = bb.forward_nhwc(x)
+        (y.float() * torch.linspace(-1, 1, y.numel(), device=y.device).view(y.shape)).sum().backward()
+
+    mtt_amd.ops.clear_pack_cache()
+    train_pass()
+    alone = set(mtt_amd.ops._packs)
+    mtt_amd.ops.clear_pack_cache()
+    model.eval()
+    with torch.no_grad():
+        bb.forward_nhwc(x)
+    assert mtt_amd.ops._packs, "the evaluation pass builds packs of its own"
+    train_pass()
+    assert set(mtt_amd.ops._packs) == alone, sorted(map(str, set(mtt_amd.ops._packs) ^ alone))
+
+
+def test_swin_eval_pass_registers_no_second_pack_set(emulated):
+    check_swin_eval_pass_registers_no_second_pack_set("cpu")
+
+
+def check_swin_training_path_checks_its_input_size(device):
+    """(shared with tests/test_gpu_train.py) an input that is not img_size raises the same assertion with and without gradients"""
+    cfg, model, x = _swin_product("mini_swin", "x3", device)
+    model.train()
+    assert any(q.requires_grad for q in model.parameters())
+    with pytest.raises(AssertionError, match="img_size"):
+        model.backbone.forward_nhwc(x[..., :-4])
+    with torch.no_grad(), pytest.raises(AssertionError, match="img_size"):
+        model.backbone.forward_nhwc(x[..., :-4])
+
+
+def test_swin_training_path_checks_its_input_size(emulated):
+    check_swin_training_path_checks_its_input_size("cpu")
 
 
 @pytest.mark.parametrize("family,name,prec", [("taskprompter", "mini_ctr", "x3f"), ("taskprompter", "mini_deconv", "bf16"), ("invpt", "mini8", "x3f"),
