@@ -4,7 +4,8 @@
 // in the C layout that IS the B fragment of the next product (reduction index permuted consistently on the A side, whose
 // fragments are two 8-byte reads of a transposed LDS tile), so P and dS never go through LDS.
 //
-//   stat[b,h,0,i] = sum_d dO[i,d] * O[i,d],  stat[b,h,1,i] = lse[i] * log2(e)                (attn_stat_kernel)
+//   stat[b,h,0,i] = sum_d dO[i,d] * O[i,d],  stat[b,h,1,i] = lse[i] * log2(e)                (VER 2: written by the dQ kernel for its own
+//                 128 rows, in attn_stat_kernel's summation order; VER 0 / VER 1: attn_stat_kernel)
 //   dQ kernel : workgroup = 128 query rows (32 per wave, B fragments of Q and dO in registers); per 64-key tile
 //                 S^T = K Q^T, dP^T = V dO^T, dS^T = P^T o (dP^T - D),   dQ^T += K^T dS^T
 //   dKV kernel: workgroup = 128 keys (32 per wave, B fragments of K and V in registers); per 64-query tile
@@ -13,6 +14,22 @@
 // logits) is therefore added to dS divided by the scale.
 #include "mtt_device.h"
 #include <type_traits>
+
+// A/B switches of the VER 2 kernels (-D...=0 through _build.build_variant restores the earlier form of one piece; VER 0 / VER 1 ignore them):
+//   MTT_ABWD_TILES  : the tile kind (full / ragged, with / without the drawlog add) is a compile-time argument of tile(); interior tiles
+//                     run a body without any end-of-sequence select
+//   MTT_ABWD_STATDMA: the dK/dV kernel's per-row D and lse*log2(e) values travel with the Q / dO tile by LDS-DMA (no ordinary global load,
+//                     hence no compiler-placed vmcnt(0), while the next tile's DMA is in flight)
+//   MTT_ABWD_DQSTAT : the dQ kernel computes D for its 128 rows and writes both stat rows; attn_stat_kernel is not launched
+#ifndef MTT_ABWD_TILES
+#define MTT_ABWD_TILES 1
+#endif
+#ifndef MTT_ABWD_STATDMA
+#define MTT_ABWD_STATDMA 1
+#endif
+#ifndef MTT_ABWD_DQSTAT
+#define MTT_ABWD_DQSTAT 1
+#endif
 
 namespace {
 
@@ -23,7 +40,16 @@ constexpr float LOG2E = 1.4426950408889634f;
 struct BwdP {
   const bf16_t* qkv; const bf16_t* dout; const float* stat; const float* drawlog; bf16_t* dqkv;
   int B, N, nH, T, Np; float scale;
+  const bf16_t* out; const float* lse; float* stat_w;   // MTT_ABWD_DQSTAT: the dQ kernel writes stat itself
 };
+
+// sum over one 8-element chunk of dO * O (packed bf16 pairs): the unit both producers of stat[.,.,0,.] add up in the same order
+MTT_DEV float dot8_bf16(const u32x4& a, const u32x4& g) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) s += lo_of(a[j]) * lo_of(g[j]) + hi_of(a[j]) * hi_of(g[j]);
+  return s;
+}
 
 __global__ __launch_bounds__(256) void attn_stat_kernel(const bf16_t* out, const bf16_t* dout, const float* lse, float* stat, int B, int N,
                                                         int nH, int Np) {
@@ -33,8 +59,7 @@ __global__ __launch_bounds__(256) void attn_stat_kernel(const bf16_t* out, const
   float s = 0.f;
   if (t < total) {
     const u32x4 a = *(const u32x4*)(out + t * 8), g = *(const u32x4*)(dout + t * 8);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s += lo_of(a[j]) * lo_of(g[j]) + hi_of(a[j]) * hi_of(g[j]);
+    s = dot8_bf16(a, g);
   }
   s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
   if (t < total && (threadIdx.x & 7) == 0) {
@@ -80,10 +105,24 @@ MTT_DEV void bwd_glds16(const bf16_t* src, unsigned char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
+MTT_DEV void bwd_glds4(const float* src, unsigned char* lds_wave_base) {   // 64 lanes x 4 B = 64 consecutive floats
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
+}
+// tile kinds of the VER 2 loops: a compile-time 0 / 1, or -1 = decided at run time (VER 0 / VER 1 and the MTT_ABWD_TILES=0 build)
+using BwdDyn = std::integral_constant<int, -1>;
+using BwdNo = std::integral_constant<int, 0>;
+using BwdYes = std::integral_constant<int, 1>;
 template <int OFF>
 MTT_DEV u32x2 bwd_ds_read_tr16(unsigned addr) {
   u32x2 r;
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
+  return r;
+}
+template <int OFF>
+MTT_DEV f32x4 bwd_ds_read_f4(unsigned addr) {
+  f32x4 r;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
   return r;
 }
 #define BWD_TRW(x) "+v"(x)
@@ -94,6 +133,10 @@ MTT_DEV u32x2 bwd_ds_read_tr16(unsigned addr) {
 #define BWD_WAIT_TR16(a, b, c, d)                                                                                                       \
   asm volatile("s_waitcnt lgkmcnt(0)" : BWD_TRW(a[0]), BWD_TRW(a[1]), BWD_TRW(a[2]), BWD_TRW(a[3]), BWD_TRW(b[0]), BWD_TRW(b[1]), BWD_TRW(b[2]), BWD_TRW(b[3]), \
                BWD_TRW(c[0]), BWD_TRW(c[1]), BWD_TRW(c[2]), BWD_TRW(c[3]), BWD_TRW(d[0]), BWD_TRW(d[1]), BWD_TRW(d[2]), BWD_TRW(d[3]) :: "memory")
+#define BWD_WAIT_TR16_F4(a, b, c, d, e, f)                                                                                              \
+  asm volatile("s_waitcnt lgkmcnt(0)" : BWD_TRW(a[0]), BWD_TRW(a[1]), BWD_TRW(a[2]), BWD_TRW(a[3]), BWD_TRW(b[0]), BWD_TRW(b[1]), BWD_TRW(b[2]), BWD_TRW(b[3]), \
+               BWD_TRW(c[0]), BWD_TRW(c[1]), BWD_TRW(c[2]), BWD_TRW(c[3]), BWD_TRW(d[0]), BWD_TRW(d[1]), BWD_TRW(d[2]), BWD_TRW(d[3]),                       \
+               BWD_TRW(e[0]), BWD_TRW(e[1]), BWD_TRW(f[0]), BWD_TRW(f[1]) :: "memory")
 
 // --------------------------------------------------------------------------------------------------------
 // VER 2 (default): LDS-DMA staging + transpose reads (above).  VER 1 (MTT_ATTN_FAST_V1): register-staged tiles with a transposed copy;
@@ -130,8 +173,36 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
       load8_raw<false>(p.dout, (tok0 + qrow) * C + h * HD + kh * 32 + lg * 8, ok, r);
       cvt8<false, false>(ok, r, gf[sub][kh], dummy);
     }
-    Dq[sub] = ok ? p.stat[bh * 2 * p.Np + qrow] : 0.f;
-    lse2[sub] = ok ? p.stat[bh * 2 * p.Np + p.Np + qrow] : 0.f;
+    if constexpr (VER == 2 && MTT_ABWD_DQSTAT) {
+      // D[q] = sum_d dO[q,d] O[q,d] in attn_stat_kernel's order: the 8-element chunk sums, then the pairwise tree over the head's eight
+      // chunks (chunk = 4 kh + lg: partner chunk ^ 1 is lane ^ 16, chunk ^ 2 is lane ^ 32, chunk ^ 4 the other kh register)
+      float c[2];
+#pragma unroll
+      for (int kh = 0; kh < 2; ++kh) {
+        Raw8<false> r;
+        u32x4 of;
+        load8_raw<false>(p.out, (tok0 + qrow) * C + h * HD + kh * 32 + lg * 8, ok, r);
+        cvt8<false, false>(ok, r, of, dummy);
+        c[kh] = dot8_bf16(of, gf[sub][kh]);
+        c[kh] += __shfl_xor(c[kh], 16, 64);
+        c[kh] += __shfl_xor(c[kh], 32, 64);
+      }
+      Dq[sub] = c[0] + c[1];
+      lse2[sub] = ok ? p.lse[bh * N + qrow] * LOG2E : 0.f;
+      if (ok && lg == 0) {
+        p.stat_w[bh * 2 * p.Np + qrow] = Dq[sub];
+        p.stat_w[bh * 2 * p.Np + p.Np + qrow] = lse2[sub];
+      }
+    } else {
+      Dq[sub] = ok ? p.stat[bh * 2 * p.Np + qrow] : 0.f;
+      lse2[sub] = ok ? p.stat[bh * 2 * p.Np + p.Np + qrow] : 0.f;
+    }
+  }
+  if constexpr (VER == 2 && MTT_ABWD_DQSTAT) {         // the head's last block zeroes the padding [N, Np) of both stat rows
+    if (qb == nqb - 1 && tid < p.Np - N) {
+      p.stat_w[bh * 2 * p.Np + N + tid] = 0.f;
+      p.stat_w[bh * 2 * p.Np + p.Np + N + tid] = 0.f;
+    }
   }
 
   const bool isK = tid < 128;
@@ -231,9 +302,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
   }
   __syncthreads();
 
-  auto tile = [&](auto stage_tag, int j) {
+  // RG: the key tile is ragged (1) / full (0); RW: the block's wave 0 adds drawlog (1) / nobody does (0); -1 = found out at run time
+  auto tile = [&](auto stage_tag, auto ragged_tag, auto raw_tag, int j) {
     constexpr int ST = decltype(stage_tag)::value;   // -1: run-time stage (VER 0)
-    const bool more = j + 1 < nkv;
+    constexpr int RG = decltype(ragged_tag)::value, RW = decltype(raw_tag)::value;
+    const bool more = RG != 1 && j + 1 < nkv;         // a tile known to be ragged at compile time is the last one
     if (more) {
       if (VER == 2) dma_issue(smem + (1 - ST) * STAGE, (j + 1) * 64);
       else stage_load((j + 1) * 64);
@@ -243,10 +316,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
     const unsigned char* Vh = Kh + 2 * KTILE;
     const int kv0 = j * 64;
     if (active) {
-      const bool full = kv0 + 64 <= N;
+      const bool full = RG < 0 ? kv0 + 64 <= N : RG == 0;
+      const bool do_raw = RW != 0 && add_raw;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {                 // two 32-key halves: keeps the live score registers at 2 x [2][2] tiles
-        if (kv0 + 32 * ks >= N) continue;              // (block-uniform) nothing valid in this half of the last tile
+        if (RG != 0 && kv0 + 32 * ks >= N) continue;   // (block-uniform) nothing valid in this half of the last tile
         f32x4 s[2][2], dp[2][2];
         u32x2 ktl[4], kth[4];                          // VER 2: K^T fragments of this half (transpose reads)
         if constexpr (VER == 2) {
@@ -319,14 +393,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
               for (int r = 0; r < 4; ++r)
                 if (kv0 + (2 * ks + k2) * 16 + lg * 4 + r >= N) ds[k2][r] = 0.f;
           }
-          if (sub == 0 && add_raw) {
+          if (sub == 0 && do_raw) {
             const float* rl = p.drawlog + (bh * p.T + li) * N;
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2)
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
                 const int key = kv0 + (2 * ks + k2) * 16 + lg * 4 + r;
-                if (key < N) ds[k2][r] += rl[key] * inv_scale;
+                if (full || key < N) ds[k2][r] += rl[key] * inv_scale;
               }
           }
           dsb[sub] = (u32x4){pack2(ds[0][0], ds[0][1]), pack2(ds[0][2], ds[0][3]), pack2(ds[1][0], ds[1][1]), pack2(ds[1][2], ds[1][3])};
@@ -350,13 +424,29 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
     }
     __syncthreads();
   };
-  if (VER >= 1) {
+  if (VER == 2 && MTT_ABWD_TILES) {
+    // full tiles run the select-free body; the ragged last tile (if any) is peeled.  Blocks whose wave 0 adds drawlog (the prompt rows'
+    // block of each head) run their own copy of the loop, so that every other block's body has no trace of the add
+    const int nfull = N / 64;
+    auto run = [&](auto raw_tag) {
+      for (int j = 0; j < nfull; j += 2) {
+        tile(BwdNo{}, BwdNo{}, raw_tag, j);
+        if (j + 1 < nfull) tile(BwdYes{}, BwdNo{}, raw_tag, j + 1);
+      }
+      if (nfull < nkv) {
+        if (nfull & 1) tile(BwdYes{}, BwdYes{}, raw_tag, nfull);
+        else tile(BwdNo{}, BwdYes{}, raw_tag, nfull);
+      }
+    };
+    if (p.drawlog != nullptr && p.T > 0 && qb == 0) run(BwdYes{});
+    else run(BwdNo{});
+  } else if (VER >= 1) {
     for (int j = 0; j < nkv; j += 2) {
-      tile(std::integral_constant<int, 0>{}, j);
-      if (j + 1 < nkv) tile(std::integral_constant<int, 1>{}, j + 1);
+      tile(BwdNo{}, BwdDyn{}, BwdDyn{}, j);
+      if (j + 1 < nkv) tile(BwdYes{}, BwdDyn{}, BwdDyn{}, j + 1);
     }
   } else {
-    for (int j = 0; j < nkv; ++j) tile(std::integral_constant<int, -1>{}, j);
+    for (int j = 0; j < nkv; ++j) tile(BwdDyn{}, BwdDyn{}, BwdDyn{}, j);
   }
   // dq[sub][dt][r] = dQ[q = li][d = 16 dt + 4 lg + r] / scale
 #pragma unroll
@@ -461,7 +551,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh) faddr[kh] = smem + li * 128 + (((kh * 4 + lg) ^ bwd_swz(li)) & 7) * 16;
   }
-  auto dma_issue = [&](unsigned char* st, int q0) {
+  const float* Drow = p.stat + bh * 2 * p.Np;
+  const float* Lrow = Drow + p.Np;
+  // MTT_ABWD_STATDMA: behind the two stages, per stage 64 D values then 64 lse*log2(e) values of the tile's query rows (wave 0 moves the
+  // D piece, wave 1 the other); a lane reads the four rows 4 lg .. 4 lg + 3 of a 16-row sub-tile as one 16-byte LDS read
+  constexpr int STAT_LDS = 2 * STAGE, STAT_STAGE = 2 * 64 * 4;
+  const unsigned saddr = (unsigned)(uintptr_t)smem + (unsigned)(lg * 16);   // read by asm like the transposed fragments: see BWD_WAIT_TR8
+  auto dma_issue = [&](unsigned char* st, unsigned char* sst, int q0) {
+    if (MTT_ABWD_STATDMA && __builtin_amdgcn_readfirstlane(wave) < 2) {
+      const float* src = (wave ? Lrow : Drow) + q0 + lane;
+      if (q0 + 64 > p.Np) src = q0 + lane < p.Np ? src : (const float*)(uintptr_t)zpage;   // rows past the zero padding of stat
+      bwd_glds4(src, sst + wave * 256);
+    }
     const bf16_t* baseQ = p.qkv + ((tok0 + q0) * 3 * C + h * HD);
     const bf16_t* baseG = p.dout + ((tok0 + q0) * C + h * HD);
     unsigned char* dQ = st + wave * 2048;
@@ -491,12 +592,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) { dk[kt][t] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[kt][t] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
   const float sc2 = p.scale * LOG2E, inv_scale = 1.0f / p.scale;
-  const float* Drow = p.stat + bh * 2 * p.Np;
-  const float* Lrow = Drow + p.Np;
 
   const int nq = (N + 63) / 64;
   if (VER == 2) {
-    dma_issue(smem, 0);
+    dma_issue(smem, smem + STAT_LDS, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   } else {
     stage_load(0);
@@ -504,11 +603,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
   }
   __syncthreads();
 
-  auto tile = [&](auto stage_tag, int j) {
+  // RG: the query tile is ragged (1) / full (0); FT: it is the first one, whose prompt rows take the drawlog add (1) / it is not (0);
+  // -1 = found out at run time
+  auto tile = [&](auto stage_tag, auto ragged_tag, auto first_tag, int j) {
     constexpr int ST = decltype(stage_tag)::value;
-    const bool more = j + 1 < nq;
+    constexpr int RG = decltype(ragged_tag)::value, FT = decltype(first_tag)::value;
+    const bool more = RG != 1 && j + 1 < nq;          // a tile known to be ragged at compile time is the last one
     if (more) {
-      if (VER == 2) dma_issue(smem + (1 - ST) * STAGE, (j + 1) * 64);
+      if (VER == 2) dma_issue(smem + (1 - ST) * STAGE, smem + STAT_LDS + (1 - ST) * STAT_STAGE, (j + 1) * 64);
       else stage_load((j + 1) * 64);
     }
     const unsigned char* Qh = smem + (ST < 0 ? (j & 1) : ST) * STAGE;
@@ -517,41 +619,61 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
     const unsigned char* Gt = Qh + 3 * KTILE;
     const int q0 = j * 64;
     if (active) {
-      const bool full = q0 + 64 <= N;
-      const bool add_raw = p.drawlog != nullptr && j == 0 && p.T > 0;
+      const bool full = RG < 0 ? q0 + 64 <= N : RG == 0;
+      const bool add_raw = FT != 0 && p.drawlog != nullptr && (FT > 0 || j == 0) && p.T > 0;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {                 // two 32-query halves
-        if (q0 + 32 * ks >= N) continue;               // (block-uniform) nothing valid in this half of the last tile
+        if (RG != 0 && q0 + 32 * ks >= N) continue;    // (block-uniform) nothing valid in this half of the last tile
         f32x4 s[2][2], dp[2][2];                       // [q sub of the half][key tile]
-        float4 D4[2], L4[2];
+        f32x4 D4[2], L4[2];
         u32x2 qtl[4], qth[4], gtl[4], gth[4];          // VER 2: Q^T / dO^T fragments of this half (transpose reads)
         if constexpr (VER == 2) {
-          u32x4 qa[2][2], ga[2][2];                    // every LDS read of the half in flight before the first MFMA
+          // a peeled ragged tile (runs once per workgroup) carries row masks on top of everything else: its transposed fragments and stat
+          // values are read after the S / dP MFMAs, when the row fragments are dead.  Every other tile has all LDS reads of the half in
+          // flight before the first MFMA
+          constexpr bool LATE = RG == 1;
+          u32x4 qa[2][2], ga[2][2];
+          auto read_stat = [&]() {
+#pragma unroll
+            for (int q2 = 0; q2 < 2; ++q2) {
+              D4[q2] = bwd_ds_read_f4<STAT_LDS + ST * STAT_STAGE>(saddr + (ks ? 128 : 0) + q2 * 64);
+              L4[q2] = bwd_ds_read_f4<STAT_LDS + ST * STAT_STAGE + 256>(saddr + (ks ? 128 : 0) + q2 * 64);
+            }
+          };
+          auto read_tr = [&]() {
+            if (ks == 0) {
+#pragma unroll
+              for (int dt = 0; dt < 4; ++dt) {
+                qtl[dt] = bwd_ds_read_tr16<ST * STAGE>(taddr[dt]); qth[dt] = bwd_ds_read_tr16<ST * STAGE + 16 * 128>(taddr[dt]);
+                gtl[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE>(taddr[dt]); gth[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE + 16 * 128>(taddr[dt]);
+              }
+            } else {
+#pragma unroll
+              for (int dt = 0; dt < 4; ++dt) {
+                qtl[dt] = bwd_ds_read_tr16<ST * STAGE + 32 * 128>(taddr[dt]); qth[dt] = bwd_ds_read_tr16<ST * STAGE + 48 * 128>(taddr[dt]);
+                gtl[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE + 32 * 128>(taddr[dt]); gth[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE + 48 * 128>(taddr[dt]);
+              }
+            }
+          };
+          auto wait_reads = [&]() {
+            if constexpr (MTT_ABWD_STATDMA) BWD_WAIT_TR16_F4(qtl, qth, gtl, gth, D4, L4);
+            else BWD_WAIT_TR16(qtl, qth, gtl, gth);
+          };
+          if constexpr (MTT_ABWD_STATDMA && !LATE) read_stat();
 #pragma unroll
           for (int q2 = 0; q2 < 2; ++q2) {
-            const int qr = q0 + (2 * ks + q2) * 16 + lg * 4;
-            D4[q2] = qr < p.Np ? *(const float4*)(Drow + qr) : make_float4(0.f, 0.f, 0.f, 0.f);
-            L4[q2] = qr < p.Np ? *(const float4*)(Lrow + qr) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (!MTT_ABWD_STATDMA) {
+              const int qr = q0 + (2 * ks + q2) * 16 + lg * 4;
+              D4[q2] = qr < p.Np ? *(const f32x4*)(Drow + qr) : (f32x4){0.f, 0.f, 0.f, 0.f};
+              L4[q2] = qr < p.Np ? *(const f32x4*)(Lrow + qr) : (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
 #pragma unroll
             for (int kh = 0; kh < 2; ++kh) {
               qa[q2][kh] = *(const u32x4*)(faddr[kh] + ST * STAGE + q2 * 2048 + (ks ? 4096 : 0));
               ga[q2][kh] = *(const u32x4*)(faddr[kh] + ST * STAGE + KTILE + q2 * 2048 + (ks ? 4096 : 0));
             }
           }
-          if (ks == 0) {
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-              qtl[dt] = bwd_ds_read_tr16<ST * STAGE>(taddr[dt]); qth[dt] = bwd_ds_read_tr16<ST * STAGE + 16 * 128>(taddr[dt]);
-              gtl[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE>(taddr[dt]); gth[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE + 16 * 128>(taddr[dt]);
-            }
-          } else {
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-              qtl[dt] = bwd_ds_read_tr16<ST * STAGE + 32 * 128>(taddr[dt]); qth[dt] = bwd_ds_read_tr16<ST * STAGE + 48 * 128>(taddr[dt]);
-              gtl[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE + 32 * 128>(taddr[dt]); gth[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE + 48 * 128>(taddr[dt]);
-            }
-          }
-          BWD_WAIT_TR16(qtl, qth, gtl, gth);
+          if constexpr (!LATE) { read_tr(); wait_reads(); }
           __builtin_amdgcn_s_setprio(1);
 #pragma unroll
           for (int q2 = 0; q2 < 2; ++q2) {
@@ -566,14 +688,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
               }
           }
           __builtin_amdgcn_s_setprio(0);
+          if constexpr (LATE) {
+            if constexpr (MTT_ABWD_STATDMA) read_stat();
+            read_tr();
+            wait_reads();
+          }
         } else {
         if (VER >= 1) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int q2 = 0; q2 < 2; ++q2) {
           const int qs = 2 * ks + q2;
           const int qr = q0 + qs * 16 + lg * 4;        // stat rows are padded to a multiple of 4 (zeros)
-          D4[q2] = qr < p.Np ? *(const float4*)(Drow + qr) : make_float4(0.f, 0.f, 0.f, 0.f);
-          L4[q2] = qr < p.Np ? *(const float4*)(Lrow + qr) : make_float4(0.f, 0.f, 0.f, 0.f);
+          D4[q2] = qr < p.Np ? *(const f32x4*)(Drow + qr) : (f32x4){0.f, 0.f, 0.f, 0.f};
+          L4[q2] = qr < p.Np ? *(const f32x4*)(Lrow + qr) : (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int kt = 0; kt < 2; ++kt) { s[q2][kt] = (f32x4){0.f, 0.f, 0.f, 0.f}; dp[q2][kt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
@@ -596,8 +723,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
           float pv[2][4], ds[2][4];
 #pragma unroll
           for (int q2 = 0; q2 < 2; ++q2) {
-            const float lr[4] = {L4[q2].x, L4[q2].y, L4[q2].z, L4[q2].w};
-            const float dr[4] = {D4[q2].x, D4[q2].y, D4[q2].z, D4[q2].w};
+            const float lr[4] = {L4[q2][0], L4[q2][1], L4[q2][2], L4[q2][3]};
+            const float dr[4] = {D4[q2][0], D4[q2][1], D4[q2][2], D4[q2][3]};
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               pv[q2][r] = __builtin_amdgcn_exp2f(fmaf(s[q2][kt][r], sc2, -lr[r]));
@@ -643,22 +770,38 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
     }
     __syncthreads();
   };
-  if (VER >= 1) {
+  if (VER == 2 && MTT_ABWD_TILES) {
+    // the first tile (drawlog add on its prompt rows) and the ragged last tile are peeled; the tiles between run the body without selects
+    const int nfull = N / 64;
+    if (nfull >= 1) tile(BwdNo{}, BwdNo{}, BwdYes{}, 0);
+    else tile(BwdNo{}, BwdYes{}, BwdYes{}, 0);
+    for (int j = 1; j < nfull; j += 2) {
+      tile(BwdYes{}, BwdNo{}, BwdNo{}, j);
+      if (j + 1 < nfull) tile(BwdNo{}, BwdNo{}, BwdNo{}, j + 1);
+    }
+    if (nfull >= 1 && nfull < nq) {
+      if (nfull & 1) tile(BwdYes{}, BwdYes{}, BwdNo{}, nfull);
+      else tile(BwdNo{}, BwdYes{}, BwdNo{}, nfull);
+    }
+  } else if (VER >= 1) {
     for (int j = 0; j < nq; j += 2) {
-      tile(std::integral_constant<int, 0>{}, j);
-      if (j + 1 < nq) tile(std::integral_constant<int, 1>{}, j + 1);
+      tile(BwdNo{}, BwdDyn{}, BwdDyn{}, j);
+      if (j + 1 < nq) tile(BwdYes{}, BwdDyn{}, BwdDyn{}, j + 1);
     }
   } else {
-    for (int j = 0; j < nq; ++j) tile(std::integral_constant<int, -1>{}, j);
+    for (int j = 0; j < nq; ++j) tile(BwdDyn{}, BwdDyn{}, BwdDyn{}, j);
   }
   // dk[kt][dt][r] = dK[key = key0 + 16 kt + li][d = 16 dt + 4 lg + r] / scale
+  int tid_e = tid;                                     // the store addresses are rebuilt from the thread index here, so that no row index or
+  asm volatile("" : "+v"(tid_e));                      // offset computed for the prologue's loads stays in a register across the loop
+  const int li_e = tid_e & 15, lg_e = (tid_e >> 4) & 3, key0_e = kb * 128 + (tid_e >> 6) * 32;
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt) {
-    const int krow = key0 + kt * 16 + li;
+    const int krow = key0_e + kt * 16 + li_e;
     if (krow >= N) continue;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
-      bf16_t* dst = p.dqkv + (tok0 + krow) * 3 * C + C + h * HD + dt * 16 + lg * 4;
+      bf16_t* dst = p.dqkv + (tok0 + krow) * 3 * C + C + h * HD + dt * 16 + lg_e * 4;
       *(u32x2*)dst = (u32x2){pack2(dk[kt][dt][0] * p.scale, dk[kt][dt][1] * p.scale), pack2(dk[kt][dt][2] * p.scale, dk[kt][dt][3] * p.scale)};
       *(u32x2*)(dst + C) = (u32x2){pack2(dv[kt][dt][0], dv[kt][dt][1]), pack2(dv[kt][dt][2], dv[kt][dt][3])};
     }
@@ -674,6 +817,7 @@ extern "C" int mtt_attn_bwd(const mtt_attn_desc* d, const void* dout, const floa
   if (((uintptr_t)d->qkv | (uintptr_t)dout | (uintptr_t)d->out | (uintptr_t)stat | (uintptr_t)dqkv) & 15) return MTT_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   constexpr int smem_dq = 2 * 3 * KTILE, smem_dkv = 2 * 4 * KTILE, smem_dma = 2 * 2 * KTILE;
+  constexpr int smem_dma_dkv = smem_dma + (MTT_ABWD_STATDMA ? 2 * 2 * 64 * 4 : 0);   // + D and lse*log2(e) of each stage's 64 query rows
   static std::atomic<unsigned long long> done_dq0{0}, done_dkv0{0}, done_dq1{0}, done_dkv1{0};
   const int ver = d->variant == MTT_ATTN_FAST_V0 ? 0 : d->variant == MTT_ATTN_FAST_V1 ? 1 : 2;
   if (ver == 0) {
@@ -685,9 +829,11 @@ extern "C" int mtt_attn_bwd(const mtt_attn_desc* d, const void* dout, const floa
   }                                                  // VER 2 stays within the default 64 KiB of dynamic LDS
   const int Np = (d->N + 3) & ~3;
   const int64_t chunks = (int64_t)d->B * d->N * d->nH * 8;
-  hipLaunchKernelGGL(attn_stat_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, (const bf16_t*)d->out, (const bf16_t*)dout,
-                     d->lse, stat, d->B, d->N, d->nH, Np);
-  BwdP p{(const bf16_t*)d->qkv, (const bf16_t*)dout, stat, d->T > 0 ? drawlog : nullptr, (bf16_t*)dqkv, d->B, d->N, d->nH, d->T, Np, d->scale};
+  if (ver != 2 || !MTT_ABWD_DQSTAT)                    // the VER 2 dQ kernel writes stat itself, ahead of the dK/dV launch on the same stream
+    hipLaunchKernelGGL(attn_stat_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, (const bf16_t*)d->out, (const bf16_t*)dout,
+                       d->lse, stat, d->B, d->N, d->nH, Np);
+  BwdP p{(const bf16_t*)d->qkv, (const bf16_t*)dout, stat, d->T > 0 ? drawlog : nullptr, (bf16_t*)dqkv, d->B, d->N, d->nH, d->T, Np, d->scale,
+         (const bf16_t*)d->out, d->lse, stat};
   dim3 grid((unsigned)(((d->N + 127) / 128) * d->nH * d->B));
   if (ver == 0) {
     hipLaunchKernelGGL(attn_bwd_dq_kernel<0>, grid, dim3(256), smem_dq, s, p);
@@ -697,7 +843,7 @@ extern "C" int mtt_attn_bwd(const mtt_attn_desc* d, const void* dout, const floa
     hipLaunchKernelGGL(attn_bwd_dkv_kernel<1>, grid, dim3(256), smem_dkv, s, p);
   } else {
     hipLaunchKernelGGL(attn_bwd_dq_kernel<2>, grid, dim3(256), smem_dma, s, p);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<2>, grid, dim3(256), smem_dma, s, p);
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel<2>, grid, dim3(256), smem_dma_dkv, s, p);
   }
   return (int)hipGetLastError();
 }

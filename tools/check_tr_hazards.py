@@ -1,4 +1,5 @@
-"""Static check of the kernels that use inline-asm LDS transpose reads (ds_read_b64_tr_b16).
+"""Static check of the kernels that use inline-asm LDS reads: transpose reads (ds_read_b64_tr_b16) and the 16-byte reads of the attention
+backward's per-row stat values (a ds_read_b128 between ;;#ASMSTART / ;;#ASMEND markers).
 
 hipcc neither counts nor waits for loads issued from inline asm, so between such a read and the `s_waitcnt lgkmcnt` that covers it the
 destination registers are IN FLIGHT: any instruction the compiler places there that touches them (typically a v_mov phi copy at a branch
@@ -27,21 +28,28 @@ def _regs(text):
     return out
 
 
+def _asm_read(lines, i):
+    """line i is an LDS read issued from inline asm: a transpose read, or a ds_read_b128 right behind an ;;#ASMSTART marker"""
+    if "ds_read_b64_tr_b16" in lines[i]:
+        return True
+    return "ds_read_b128" in lines[i] and i > 0 and "#ASMSTART" in lines[i - 1]
+
+
 def check_asm(lines):
-    """-> (blocks, problems): every run of transpose reads up to the lgkmcnt(0) wait that retires it."""
+    """-> (blocks, problems): every run of inline-asm reads up to the lgkmcnt(0) wait that retires it."""
     blocks, problems, i = 0, [], 0
     func = "?"
     while i < len(lines):
         if lines[i].startswith("_Z") and lines[i].rstrip().endswith(":"):
             func = lines[i].split(":")[0]
-        if "ds_read_b64_tr_b16" not in lines[i]:
+        if not _asm_read(lines, i):
             i += 1
             continue
         blocks += 1
         inflight, j, done = [], i, False
         while j < len(lines):
             t = lines[j].strip()
-            if "ds_read_b64_tr_b16" in t:
+            if _asm_read(lines, j):
                 m = re.search(r"v\[(\d+):(\d+)\]", t)
                 inflight.append(set(range(int(m.group(1)), int(m.group(2)) + 1)))
             elif t.startswith("s_waitcnt") and "lgkmcnt(0)" in t:
