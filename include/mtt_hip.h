@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTT_ABI_VERSION 15
+#define MTT_ABI_VERSION 16
 
 /* MTT_SPLIT: an fp32-class value stored as TWO bf16 planes of identical layout, x = hi + lo with hi = bf16(x), lo = bf16(x - hi)
  * (~16 mantissa bits).  The main pointer of an operand addresses the hi plane, its `*_lo` companion the lo plane.  The hi plane alone is
@@ -695,6 +695,56 @@ size_t mtt_fcos3d_ws_floats(const mtt_fcos3d_desc* d);
 int mtt_fcos3d_targets(const mtt_fcos3d_desc* d, void* stream);
 int mtt_fcos3d_loss_fwd(const mtt_fcos3d_desc* d, void* stream);
 int mtt_fcos3d_loss_bwd(const mtt_fcos3d_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * ABI 16 — FCOS3D box decoding and per-class NMS of the 3ddet task at inference (det_model.py get_bboxes / _get_bboxes_single :483-681,
+ * det_tools.py box3d_multiclass_nms :85-210).  New entry points only; all four take one descriptor and read / write only the buffers
+ * named below, all caller-owned.  Maps: the head's NCHW fp32 maps as in ABI 15's descriptor, 13 regression channels; points as there.
+ *
+ * Candidates: level l contributes n_l = nms_pre when nms_pre > 0 and P_l > nms_pre, else P_l; cand_off[l] = sum of the earlier n_l and
+ *   cand_off[nlev] = N (N <= MTT_DET_MAX_CAND, C <= MTT_DET_MAX_CLASSES).  key_off is the same for P_l (key_off[nlev] = P).
+ * mtt_det_select: one workgroup per (level, image).  keys[b, key_off[l] + p] = max_c sigmoid(cls_c) * sigmoid(ctr); sel[b, cand_off[l]
+ *   + i] = the level-local point index of the i-th selected point: the n_l largest keys (a radix select on the fp32 bit pattern, the
+ *   histogram in LDS; among keys equal to the n_l-th largest the lowest point indices), in ascending point order; the whole level in
+ *   order when n_l == P_l.
+ * mtt_det_decode: one thread per (image, candidate).  denorm[l] multiplies the offset and the 2-D distances (the level's stride for the
+ *   head's normalised maps, 1 for denormalised ones).  box9 [B, N, 9] = (camera centre = (u d, v d, d, 1) . inv[b]^T, size, the three
+ *   angles rot - floor((rot - dir_offset) / pi) pi + pi dir_cls), cen2d [B, N, 3] = (u, v, d) with (u, v) = point - offset, box2d
+ *   [B, N, 4] = point -/+ distances clamped to [0, img_size[b] = (H, W)], nmsbox [B, N, 5] = columns (0, 2, 4, 3, 8) of box9 as
+ *   (x - w/2, z - l/2, x + w/2, z + l/2, yaw), dircls int32 [B, N, 3] (1 when the second logit is larger), scores [B, N, C] =
+ *   sigmoid(cls) * sigmoid(ctr).  inv fp32 [B, 16]: the row-major inverse of the 4 x 4 padded camera matrix.
+ * mtt_det_nms_seg: one segment per (image, class): the candidates with scores > score_thr, sorted by descending score (bitonic, in LDS;
+ *   equal scores by ascending candidate index), the 64 x 64 suppression masks of mtt_nms_bev's kernels on them (rotated = 1 / 0) and its
+ *   greedy pass, all on the device.  seg_n int32 [B, C] = candidates above the threshold, seg_idx int32 [B, C, N] = their candidate
+ *   indices in sorted order, kept_n int32 [B, C], kept int32 [B, C, N] = the kept candidates' indices in score order; ws >=
+ *   mtt_det_nms_ws_bytes(d) bytes (sorted scores and boxes, kept scores, masks).
+ * mtt_det_collect: the kept lists concatenated in class order; when more than max_per_img remain, the max_per_img best by descending
+ *   score (equal scores in concatenation order).  out fp32 [B, max_per_img, 18] = (box9, score, cen2d, box2d, the label's int32 bit
+ *   pattern), count int32 [B]; rows at and beyond count[b] are not written.  Reads kept / kept_n and ws of mtt_det_nms_seg.
+ * No allocation, synchronisation or atomics on floats; bitwise reproducible. */
+#define MTT_DET_MAX_CAND 8192
+#define MTT_DET_MAX_CLASSES 16
+#define MTT_DET_OUT_COLS 18
+typedef struct {
+  const float* cls[8]; const float* bbox[8]; const float* dir[8]; const float* ctr[8];
+  int32_t H[8], W[8];
+  float stride[8], half[8], denorm[8];
+  int32_t cand_off[9], key_off[9];
+  int32_t nlev, B, C, N, nms_pre, rotated, max_per_img;
+  float dir_offset, score_thr, nms_thr;
+  const float* inv; const float* img_size;
+  float* keys; int32_t* sel;
+  float* box9; float* cen2d; float* box2d; float* nmsbox; int32_t* dircls; float* scores;
+  int32_t* seg_n; int32_t* seg_idx; int32_t* kept_n; int32_t* kept;
+  void* ws;
+  float* out; int32_t* count;
+} mtt_det_decode_desc;
+size_t mtt_det_decode_desc_size(void);
+size_t mtt_det_nms_ws_bytes(const mtt_det_decode_desc* d);
+int mtt_det_select(const mtt_det_decode_desc* d, void* stream);
+int mtt_det_decode(const mtt_det_decode_desc* d, void* stream);
+int mtt_det_nms_seg(const mtt_det_decode_desc* d, void* stream);
+int mtt_det_collect(const mtt_det_decode_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

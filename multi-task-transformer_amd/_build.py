@@ -8,12 +8,12 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libmtt_hip.so")
-SOURCES = ["gemm.hip", "attn.hip", "attn_fast.hip", "attn_bwd.hip", "rowops.hip", "invpt_ops.hip", "optim.hip", "loss.hip", "upconv.hip", "swin_ops.hip", "iou3d.hip", "det_ops.hip", "det_loss3d.hip"]
+SOURCES = ["gemm.hip", "attn.hip", "attn_fast.hip", "attn_bwd.hip", "rowops.hip", "invpt_ops.hip", "optim.hip", "loss.hip", "upconv.hip", "swin_ops.hip", "iou3d.hip", "det_ops.hip", "det_loss3d.hip", "det_decode.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 
 
 def _stamp(src, deps):
-    """what an object was compiled from: sha256 over the source, the two shared headers and the flags (NOT mtimes: a snapshot copied to
+    """what an object was compiled from: sha256 over the source, the shared headers and the flags (NOT mtimes: a snapshot copied to
     another box keeps its contents, not its timestamps)"""
     import hashlib
     h = hashlib.sha256(" ".join(f for f in FLAGS if not f.startswith("-I")).encode())
@@ -28,7 +28,7 @@ def build(force=False, verbose=False):
     recompiles everything."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     force = force or os.environ.get("MTT_FORCE_BUILD") == "1"
-    deps = [os.path.join(CSRC, "mtt_device.h"), os.path.join(ROOT, "include", "mtt_hip.h")]
+    deps = [os.path.join(CSRC, "mtt_device.h"), os.path.join(CSRC, "iou3d_dev.h"), os.path.join(ROOT, "include", "mtt_hip.h")]
     objs, jobs, stamps, wants = [], [], {}, {}
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -16,7 +16,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmtt_hip.so")
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 F32, BF16, SPLIT = 0, 1, 2
 PREC_BF16, PREC_X3 = 0, 1
 OP_K, OP_R, OP_CONV_K, OP_CONV_R = 0, 1, 2, 3
@@ -223,6 +223,21 @@ class Fcos3dDesc(C.Structure):
                 ("gamma", f32), ("alpha", f32), ("beta", f32), ("beta2d", f32), ("ctr_alpha", f32), ("dir_offset", f32)]
 
 
+class DetDecodeDesc(C.Structure):
+    _fields_ = [("cls", ptr * 8), ("bbox", ptr * 8), ("dir", ptr * 8), ("ctr", ptr * 8),
+                ("H", i32 * 8), ("W", i32 * 8),
+                ("stride", f32 * 8), ("half", f32 * 8), ("denorm", f32 * 8),
+                ("cand_off", i32 * 9), ("key_off", i32 * 9),
+                ("nlev", i32), ("B", i32), ("C", i32), ("N", i32), ("nms_pre", i32), ("rotated", i32), ("max_per_img", i32),
+                ("dir_offset", f32), ("score_thr", f32), ("nms_thr", f32),
+                ("inv", ptr), ("img_size", ptr),
+                ("keys", ptr), ("sel", ptr),
+                ("box9", ptr), ("cen2d", ptr), ("box2d", ptr), ("nmsbox", ptr), ("dircls", ptr), ("scores", ptr),
+                ("seg_n", ptr), ("seg_idx", ptr), ("kept_n", ptr), ("kept", ptr),
+                ("ws", ptr),
+                ("out", ptr), ("count", ptr)]
+
+
 # entry point -> (descriptor struct, size index in mtt_desc_size) ; None = positional-argument entry
 DESCS = {
     "loss_fwd": LossDesc,
@@ -282,11 +297,16 @@ DESC_EXTRA = {
     "convt3x3s2_gather_bwd": (ConvtDesc, [ptr, ptr]),
 }
 
+# ABI 16: the inference post-processing of the 3ddet task (csrc/det_decode.hip), descriptor entry points like DESCS.  A table of its own:
+# the kernel parity suite enumerates DESCS | POSITIONAL | DESC_EXTRA, and these are covered by tests/test_gpu_det_decode.py instead.
+POSTPROC = {"det_select": DetDecodeDesc, "det_decode": DetDecodeDesc, "det_nms_seg": DetDecodeDesc, "det_collect": DetDecodeDesc}
+DET_MAX_CAND, DET_MAX_CLASSES, DET_OUT_COLS = 8192, 16, 18            # MTT_DET_* of include/mtt_hip.h
+
 # workspace-size queries mtt_<entry>_ws_floats(const desc*) of the entry points whose cross-workgroup reductions go through caller-owned partials
 WS_QUERIES = {"gemm_colsum": GemmDesc, "chan_logits": ChanLogitDesc, "modulate_bwd": ModulateDesc, "ctr_dw": CtrDesc, "attn_msg_bwd": AttnMsgDesc, "loss": LossDesc,
               "chanattn_bwd": ChanAttnDesc, "detloss": DetLossDesc,
               "groupnorm": GnDesc, "dcn_col2im": DcnDesc, "fcos_bbox_post": BboxPostDesc, "fcos3d": Fcos3dDesc}
-EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_fcos3d_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA)]
+EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_fcos3d_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes", "mtt_det_decode_desc_size", "mtt_det_nms_ws_bytes"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA) + list(POSTPROC)]
 
 _lib = None
 
@@ -324,7 +344,13 @@ def load():
     lib.mtt_fcos3d_desc_size.argtypes = []
     if lib.mtt_fcos3d_desc_size() != C.sizeof(Fcos3dDesc):                           # ABI 15
         raise RuntimeError(f"descriptor layout mismatch for Fcos3dDesc: C {lib.mtt_fcos3d_desc_size()} vs ctypes {C.sizeof(Fcos3dDesc)}")
-    for name, st in DESCS.items():
+    lib.mtt_det_decode_desc_size.restype = C.c_size_t
+    lib.mtt_det_decode_desc_size.argtypes = []
+    if lib.mtt_det_decode_desc_size() != C.sizeof(DetDecodeDesc):                    # ABI 16
+        raise RuntimeError(f"descriptor layout mismatch for DetDecodeDesc: C {lib.mtt_det_decode_desc_size()} vs ctypes {C.sizeof(DetDecodeDesc)}")
+    lib.mtt_det_nms_ws_bytes.restype = C.c_size_t
+    lib.mtt_det_nms_ws_bytes.argtypes = [C.POINTER(DetDecodeDesc)]
+    for name, st in list(DESCS.items()) + list(POSTPROC.items()):
         fn = getattr(lib, "mtt_" + name)
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(st), ptr]
@@ -350,6 +376,14 @@ def ws_floats(entry, **fields):
     fn.restype = C.c_size_t
     fn.argtypes = [C.POINTER(WS_QUERIES[entry])]
     return int(fn(C.byref(desc)))
+
+
+def det_nms_ws_bytes(batch, classes, cands):
+    """mtt_det_nms_ws_bytes for `batch` images, `classes` classes and `cands` candidates per image"""
+    lib = load()
+    desc = DetDecodeDesc()
+    desc.B, desc.C, desc.N = int(batch), int(classes), int(cands)
+    return int(lib.mtt_det_nms_ws_bytes(C.byref(desc)))
 
 
 def dtype_code(t):
@@ -405,7 +439,7 @@ def call(name, **kw):
             desc = st()
             extra = [(_addr(a) if isinstance(a, torch.Tensor) else a) for a in kw["xargs"]]
         else:
-            desc = DESCS[name]()
+            desc = (POSTPROC[name] if name in POSTPROC else DESCS[name])()
         for k, v in kw.items():
             if k == "xargs":
                 continue

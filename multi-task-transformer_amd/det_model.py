@@ -1,5 +1,6 @@
-"""The FCOS3D criterion of the 3ddet task: `DetModel` of TaskPrompter/detection_toolbox/det_model.py (constructor :41-127, `loss`
-:253-481, `get_points` / `get_targets` :717-955), with `pred_bbox2d=True` as the Cityscapes-3D config builds it.
+"""The FCOS3D criterion and box decoding of the 3ddet task: `DetModel` of TaskPrompter/detection_toolbox/det_model.py (constructor
+:41-127, `loss` :253-481, `get_bboxes` :483-681, `get_points` / `get_targets` :717-955, `get_results_from_bbox` :957-1002), with
+`pred_bbox2d=True` as the Cityscapes-3D config builds it.
 
 `DetModel.loss(preds, labels) -> (loss_dict, loss_sum)` takes the head's per-level NCHW fp32 lists (FCOS3DHead.forward) and the
 reference's collated labels.  The host packs the ragged gt lists into one device buffer (shapes and the per-image `det_label_number`
@@ -12,14 +13,20 @@ Differences from the reference, all outside its arithmetic:
   with no positives every positive-only term is exactly 0, as the reference's sums over empty tensors are;
 - the constructor copies the loss config dicts instead of deleting their 'type' keys, so one parameter dict can build several criteria;
 - options the kernels do not implement raise NotImplementedError naming the option.
-Decoding (`get_bboxes`, NMS, back-projection) is not built.
+
+`DetModel.get_results_from_bbox(preds, label, rescale=False)` and `get_bboxes(...)` decode the same maps at inference: pre-selection,
+back-projection through the camera matrix, the direction classes, per-class rotated (or axis-aligned) NMS and the per-image cap all run
+in the HIP kernels of csrc/det_decode.hip with fixed-capacity buffers; the one host synchronisation is the final device-to-host copy of
+the kept rows and their counts (the reference synchronises once per class and again inside every NMS call).  The order of exactly equal
+scores is unspecified, as in the reference; `rescale=True` raises NotImplementedError (the reference raises there too with pred_bbox2d).
 """
 import copy
 
+import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import det_decode, ops
 
 INF = 1e8
 LOSS_KEYS = ('loss_cls', 'loss_offset', 'loss_depth', 'loss_size', 'loss_rotsin', 'loss_dir', 'loss_centerness', 'loss_bbox2d')
@@ -303,6 +310,93 @@ class DetModel(nn.Module):
             return {}, out[8]
         return {k: out[i] for i, k in enumerate(LOSS_KEYS)}, out[8]
 
+    # ---- inference: box decoding -------------------------------------------------------------------------------------------------
+    def _test_cfg(self, cfg):
+        """the reference's test_cfg (a dict or an attribute object) -> the five options the decode path reads"""
+        cfg = self.test_cfg if cfg is None else cfg
+        if cfg is None:
+            raise ValueError("DetModel was built without a test_cfg (see cs_test_cfg())")
+        get = (lambda k: cfg[k]) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k))
+        out = dict(use_rotate_nms=bool(get('use_rotate_nms')), nms_pre=int(get('nms_pre')), nms_thr=float(get('nms_thr')),
+                   score_thr=float(get('score_thr')), max_per_img=int(get('max_per_img')))
+        if out['max_per_img'] <= 0:
+            raise NotImplementedError(f"test_cfg: max_per_img={out['max_per_img']} (the output capacity; only > 0 is implemented)")
+        return out
+
+    def _decode(self, cls_scores, bbox_preds, dir_cls_preds, centernesses, img_metas, cfg, rescale, denorm):
+        if rescale:
+            raise NotImplementedError("DetModel: rescale=True is not implemented (the reference raises there as well when pred_bbox2d is set)")
+        cfg = self._test_cfg(cfg)
+        L = len(cls_scores)
+        if not (len(bbox_preds) == len(dir_cls_preds) == len(centernesses) == L):
+            raise ValueError("the four prediction lists differ in length")
+        maps = (list(cls_scores), list(bbox_preds), list(dir_cls_preds), list(centernesses))
+        for m in (m for lst in maps for m in lst):
+            if not m.is_cuda:
+                raise RuntimeError("DetModel box decoding runs on the HIP kernels: predictions must be on the GPU (no CPU path)")
+            if m.dtype != torch.float32:
+                raise RuntimeError(f"DetModel box decoding takes fp32 predictions, got {m.dtype}")
+            if m.dim() != 4:
+                raise ValueError("DetModel box decoding takes NCHW prediction maps")
+        dev = cls_scores[0].device
+        B, C = len(img_metas), self.num_classes
+        sizes = [tuple(c.shape[-2:]) for c in cls_scores]
+        for lv in range(L):
+            H, W = sizes[lv]
+            for m, ch, what in ((cls_scores[lv], C, 'cls_scores'), (bbox_preds[lv], 13, 'bbox_preds'),
+                                (dir_cls_preds[lv], 6, 'dir_cls_preds'), (centernesses[lv], 1, 'centernesses')):
+                if tuple(m.shape) != (B, ch, H, W):
+                    raise ValueError(f"{what}[{lv}] has shape {tuple(m.shape)}, expected {(B, ch, H, W)}")
+        geo = det_decode.geometry(sizes, self.strides, cfg['nms_pre'], denorm)
+        bufs = det_decode.buffers(B, C, geo, cfg['max_per_img'], dev)
+        # per image: the inverse of the 4 x 4 padded camera matrix, fp32 on the host as points_img2cam (det_tools.py:639-641) takes it
+        # from the loader's matrix, and img_size = (H, W)
+        host = torch.zeros(B, 18, dtype=torch.float32)
+        for b, meta in enumerate(img_metas):
+            K = torch.as_tensor(meta['K_matrix']).detach().to(device='cpu', dtype=torch.float32)
+            if K.dim() != 2 or K.shape[0] > 4 or K.shape[1] > 4:
+                raise ValueError(f"K_matrix of image {b} has shape {tuple(K.shape)}")
+            padded = torch.eye(4, dtype=torch.float32)
+            padded[:K.shape[0], :K.shape[1]] = K
+            host[b, :16] = torch.inverse(padded).reshape(16)
+            host[b, 16], host[b, 17] = float(meta['img_size'][0]), float(meta['img_size'][1])
+        host = host.to(dev, non_blocking=True)
+        det_decode.run(tuple([m.detach().contiguous() for m in lst] for lst in maps), geo, bufs, B, C, host[:, :16].contiguous(),
+                       host[:, 16:].contiguous(), dir_offset=self.dir_offset, score_thr=cfg['score_thr'], nms_thr=cfg['nms_thr'],
+                       rotated=cfg['use_rotate_nms'], max_per_img=cfg['max_per_img'])
+        packed = bufs['packed'].cpu()                                                    # the one host synchronisation
+        M, cols = cfg['max_per_img'], det_decode.OUT_COLS
+        rows = packed[:B * M * cols].view(B, M, cols)
+        count = packed[B * M * cols:].view(torch.int32)
+        out = []
+        for b in range(B):
+            r = rows[b, :int(count[b])]
+            scores = r[:, 9].clone()
+            out.append((r[:, :9].clone(), scores, r[:, 17].contiguous().view(torch.int32).long(), r[:, 10:13].clone(),
+                        torch.cat([r[:, 13:17], scores[:, None]], dim=1)))
+        return out
+
+    def get_bboxes(self, cls_scores, bbox_preds, dir_cls_preds, centernesses, img_metas, cfg=None, rescale=None):
+        """(:483-553) per-level NCHW fp32 maps with ALREADY DENORMALISED bbox_preds, one meta dict per image (K_matrix, img_size) ->
+        per image (bboxes [n, 9], scores [n], labels [n] int64, centers2d [n, 3], bboxes2d [n, 5] = box + score), CPU tensors."""
+        return self._decode(cls_scores, bbox_preds, dir_cls_preds, centernesses, img_metas, cfg, rescale, denorm=False)
+
+    def get_results_from_bbox(self, preds, label, rescale=False):
+        """(:957-1002) preds = the head's (cls_scores, bbox_preds, dir_cls_preds, centernesses); label['meta'] = the collated meta dict
+        (img_name, K_matrix, img_size per image) -> per image dict(img_bbox=dict(boxes_3d, scores_3d, labels_3d, centers2d),
+        img_bbox2d = numpy [n, 5], or the reference's list of num_classes empty (0, 5) float64 arrays when n == 0).
+        `denorm_on_bbox` (:231-250) is not built as a separate method: the decode kernel multiplies the offsets and the 2-D distances
+        by the level's stride as it reads them, instead of materialising denormalised copies of every bbox map."""
+        bs = len(label['meta']['img_name'])
+        img_metas = [{k: v[s] for k, v in label['meta'].items()} for s in range(bs)]
+        cls_scores, bbox_preds, dir_cls_preds, centernesses = preds
+        outs = self._decode(cls_scores, bbox_preds, dir_cls_preds, centernesses, img_metas, self.test_cfg, rescale, denorm=self.norm_on_bbox)
+        results = []
+        for bboxes, scores, labels, centers2d, bboxes2d in outs:
+            b2 = [np.zeros((0, 5), dtype=np.float64) for _ in range(self.num_classes)] if bboxes2d.shape[0] == 0 else bboxes2d.numpy()
+            results.append(dict(img_bbox=dict(boxes_3d=bboxes, scores_3d=scores, labels_3d=labels, centers2d=centers2d), img_bbox2d=b2))
+        return results
+
     # ---- inspection --------------------------------------------------------------------------------------------------------------
     def get_points(self, featmap_sizes, dtype, device, flatten=False):
         """points of every level (:717-754): [H*W, 2] = (x * stride, y * stride) + stride // 2"""
@@ -347,6 +441,12 @@ class DetModel(nn.Module):
 
 
 # ---- configuration ---------------------------------------------------------------------------------------------------------------
+def cs_test_cfg():
+    """test_cfg of TaskPrompter/configs/cityscapes3d/det_head_params.py:4-12 (nms_across_levels and min_bbox_size are carried as the
+    reference carries them: its decode path never reads them)"""
+    return dict(use_rotate_nms=True, nms_across_levels=False, nms_pre=1000, nms_thr=0.3, score_thr=0.05, min_bbox_size=0, max_per_img=200)
+
+
 def cs_det_model_params():
     """det_model_params of TaskPrompter/configs/cityscapes3d/det_head_params.py (the Cityscapes-3D config), strides not yet scaled"""
     return dict(
@@ -360,7 +460,7 @@ def cs_det_model_params():
         loss_consistency=dict(type='GIoULoss', loss_weight=1.0), stacked_convs=3, strides=[8, 16, 32, 32, 64],
         use_direction_classifier=True, background_label=None, diff_rad_by_sin=True, dir_offset=0, bbox_code_size=9, pred_bbox2d=True,
         pred_keypoints=False, group_reg_dims=(2, 1, 3, 3, 4),
-        code_weight=[1.0, 1.0, 0.2, 1.0, 1.0, 1.0, 5.0, 5.0, 5.0, 1.0, 1.0, 1.0, 1.0], test_cfg=None)
+        code_weight=[1.0, 1.0, 0.2, 1.0, 1.0, 1.0, 5.0, 5.0, 5.0, 1.0, 1.0, 1.0, 1.0], test_cfg=cs_test_cfg())
 
 
 def configure_3ddet(p, det_model_params=None):
