@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTT_ABI_VERSION 16
+#define MTT_ABI_VERSION 17
 
 /* MTT_SPLIT: an fp32-class value stored as TWO bf16 planes of identical layout, x = hi + lo with hi = bf16(x), lo = bf16(x - hi)
  * (~16 mantissa bits).  The main pointer of an operand addresses the hi plane, its `*_lo` companion the lo plane.  The hi plane alone is
@@ -745,6 +745,51 @@ int mtt_det_select(const mtt_det_decode_desc* d, void* stream);
 int mtt_det_decode(const mtt_det_decode_desc* d, void* stream);
 int mtt_det_nms_seg(const mtt_det_decode_desc* d, void* stream);
 int mtt_det_collect(const mtt_det_decode_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * ABI 17 — evaluation of the dense tasks on the device: what the reference's validation loop computes between model(images) and
+ * get_score (TaskPrompter/utils/utils.py get_output :27-63; evaluation/eval_semseg.py, eval_human_parts.py, eval_sal.py, eval_depth.py,
+ * eval_normals.py, eval_edge.py).  New entry points only.  Logits fp32 NCHW [B, C, HW], labels fp32 [B, Cl, HW]; fp32 arithmetic in the
+ * reference's operation order (no contraction into FMAs); one thread per pixel, or per four consecutive pixels (16-byte loads) when HW is a
+ * multiple of 4 and pred, label and out are 16-byte aligned: which of the two runs is a function of the descriptor alone, and fixes the
+ * order in which the fp64 partial sums are taken.
+ *
+ * kind                 C / Cl   map (mtt_eval_map -> out)                                accumulator `acc` (8-byte slots, caller zeroes)
+ *  MTT_EVAL_CONFUSION  C / 1    int64 [B, HW]: arg-max over C, first index wins ties;    int64 tp[n], fp[n], fn[n]  (n <= 256, HW < 2^32)
+ *                               class_map (int64 [n_map], optional): p < n_map -> map[p]
+ *  MTT_EVAL_SAL        2 / 1    fp32 [B, HW]: 255 * softmax(x)[1]                        int64 pp_hist[T + 1], tp_hist[T + 1], ap  (T <= 255)
+ *  MTT_EVAL_DEPTH      1 / 1    fp32 [B, HW]: max(x, 0); out may be pred (in place)      int64 count; fp64 sum (g-v)^2, (log g - log v)^2,
+ *                                                                                        |g-v|/g, (g-v)^2/g
+ *  MTT_EVAL_NORMALS    3 / 3    fp32 [B, HW, 3]: (x / max(|x|, 1e-12) + 1) * 255 / 2     int64 count; fp64 sum of the angle in degrees
+ *  MTT_EVAL_EDGE       1 / 1    fp32 [B, HW]: 255 / (1 + exp(-x))                        int64 count; fp64 sum of term / factor
+ *
+ * mtt_eval_accum adds one batch to `acc`.  source = MTT_EVAL_FROM_LOGITS: pred = the logits; MTT_EVAL_FROM_MAP: pred = the map that
+ * mtt_eval_map wrote (int64 for CONFUSION).  Both sources feed the same per-pixel value into the same code: bitwise equal accumulators.
+ * valid pixel: label != ignore (all three channels for NORMALS); DEPTH with mask_mode 0: min_depth < label < max_depth, 1: label != ignore.
+ *   CONFUSION  p = arg-max, g = label: g == p < n -> tp[p]; otherwise fp[p] when 0 <= p < n and fn[g] when g is an integer in [0, n)
+ *   SAL        s = sigmoid(map / 255) (the reference squashes the probability a second time), k = #{i : s >= thresholds[i]} (fp32 [T],
+ *              ascending), t = (int64) label: pp_hist[k] += 1, tp_hist[k] += t, ap += t
+ *   DEPTH      g' = g <= 0 ? 1e-9 : g, v' likewise from v = max(x, 0)
+ *   NORMALS    p = normalize(2 map / 255 - 1), g = normalize(label) (a zero norm gives the zero vector): deg(2 atan2(|p - g|, |p + g|))
+ *   EDGE       z = map / 255, w = pos_weight, factor = 1 / (1 - w), pw = w factor: term = (1 - y) z + (1 + (pw - 1) y) softplus(-z)
+ * Integer counters: a histogram per workgroup in LDS, then 64-bit integer atomics on acc (order-independent).  fp64 sums: no atomics;
+ * per-workgroup partials go to ws (>= mtt_eval_ws_floats(d) floats, 8-byte aligned; 0 for the integer-only kinds) and a second launch
+ * adds them to acc in workgroup order.  Neither entry point modifies its inputs, except mtt_eval_map when out aliases pred (DEPTH). */
+enum { MTT_EVAL_CONFUSION = 0, MTT_EVAL_SAL = 1, MTT_EVAL_DEPTH = 2, MTT_EVAL_NORMALS = 3, MTT_EVAL_EDGE = 4 };
+enum { MTT_EVAL_FROM_LOGITS = 0, MTT_EVAL_FROM_MAP = 1 };
+typedef struct {
+  const void* pred; const float* label;
+  void* out;                       /* mtt_eval_map */
+  void* acc; double* ws;           /* mtt_eval_accum */
+  const float* thresholds; const int64_t* class_map;
+  int64_t B, HW;
+  int32_t C, Cl, kind, source, n_classes, n_thresh, n_map, mask_mode;
+  float ignore, pos_weight, min_depth, max_depth;
+} mtt_eval_desc;
+size_t mtt_eval_desc_size(void);
+size_t mtt_eval_ws_floats(const mtt_eval_desc* d);
+int mtt_eval_map(const mtt_eval_desc* d, void* stream);
+int mtt_eval_accum(const mtt_eval_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

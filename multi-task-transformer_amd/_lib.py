@@ -16,7 +16,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmtt_hip.so")
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 F32, BF16, SPLIT = 0, 1, 2
 PREC_BF16, PREC_X3 = 0, 1
 OP_K, OP_R, OP_CONV_K, OP_CONV_R = 0, 1, 2, 3
@@ -238,6 +238,13 @@ class DetDecodeDesc(C.Structure):
                 ("out", ptr), ("count", ptr)]
 
 
+class EvalDesc(C.Structure):
+    _fields_ = [("pred", ptr), ("label", ptr), ("out", ptr), ("acc", ptr), ("ws", ptr), ("thresholds", ptr), ("class_map", ptr),
+                ("B", i64), ("HW", i64),
+                ("C", i32), ("Cl", i32), ("kind", i32), ("source", i32), ("n_classes", i32), ("n_thresh", i32), ("n_map", i32), ("mask_mode", i32),
+                ("ignore", f32), ("pos_weight", f32), ("min_depth", f32), ("max_depth", f32)]
+
+
 # entry point -> (descriptor struct, size index in mtt_desc_size) ; None = positional-argument entry
 DESCS = {
     "loss_fwd": LossDesc,
@@ -302,11 +309,17 @@ DESC_EXTRA = {
 POSTPROC = {"det_select": DetDecodeDesc, "det_decode": DetDecodeDesc, "det_nms_seg": DetDecodeDesc, "det_collect": DetDecodeDesc}
 DET_MAX_CAND, DET_MAX_CLASSES, DET_OUT_COLS = 8192, 16, 18            # MTT_DET_* of include/mtt_hip.h
 
+# ABI 17: evaluation of the dense tasks (csrc/eval_ops.hip), descriptor entry points like DESCS.  A table of its own as well: covered by
+# tests/test_gpu_eval.py.
+EVAL = {"eval_map": EvalDesc, "eval_accum": EvalDesc}
+EVAL_CONFUSION, EVAL_SAL, EVAL_DEPTH, EVAL_NORMALS, EVAL_EDGE = 0, 1, 2, 3, 4     # MTT_EVAL_* of include/mtt_hip.h
+EVAL_FROM_LOGITS, EVAL_FROM_MAP = 0, 1
+
 # workspace-size queries mtt_<entry>_ws_floats(const desc*) of the entry points whose cross-workgroup reductions go through caller-owned partials
 WS_QUERIES = {"gemm_colsum": GemmDesc, "chan_logits": ChanLogitDesc, "modulate_bwd": ModulateDesc, "ctr_dw": CtrDesc, "attn_msg_bwd": AttnMsgDesc, "loss": LossDesc,
               "chanattn_bwd": ChanAttnDesc, "detloss": DetLossDesc,
               "groupnorm": GnDesc, "dcn_col2im": DcnDesc, "fcos_bbox_post": BboxPostDesc, "fcos3d": Fcos3dDesc}
-EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_fcos3d_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes", "mtt_det_decode_desc_size", "mtt_det_nms_ws_bytes"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA) + list(POSTPROC)]
+EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_fcos3d_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes", "mtt_det_decode_desc_size", "mtt_det_nms_ws_bytes", "mtt_eval_desc_size", "mtt_eval_ws_floats"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA) + list(POSTPROC) + list(EVAL)]
 
 _lib = None
 
@@ -350,7 +363,13 @@ def load():
         raise RuntimeError(f"descriptor layout mismatch for DetDecodeDesc: C {lib.mtt_det_decode_desc_size()} vs ctypes {C.sizeof(DetDecodeDesc)}")
     lib.mtt_det_nms_ws_bytes.restype = C.c_size_t
     lib.mtt_det_nms_ws_bytes.argtypes = [C.POINTER(DetDecodeDesc)]
-    for name, st in list(DESCS.items()) + list(POSTPROC.items()):
+    lib.mtt_eval_desc_size.restype = C.c_size_t
+    lib.mtt_eval_desc_size.argtypes = []
+    if lib.mtt_eval_desc_size() != C.sizeof(EvalDesc):                               # ABI 17
+        raise RuntimeError(f"descriptor layout mismatch for EvalDesc: C {lib.mtt_eval_desc_size()} vs ctypes {C.sizeof(EvalDesc)}")
+    lib.mtt_eval_ws_floats.restype = C.c_size_t
+    lib.mtt_eval_ws_floats.argtypes = [C.POINTER(EvalDesc)]
+    for name, st in list(DESCS.items()) + list(POSTPROC.items()) + list(EVAL.items()):
         fn = getattr(lib, "mtt_" + name)
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(st), ptr]
@@ -384,6 +403,14 @@ def det_nms_ws_bytes(batch, classes, cands):
     desc = DetDecodeDesc()
     desc.B, desc.C, desc.N = int(batch), int(classes), int(cands)
     return int(lib.mtt_det_nms_ws_bytes(C.byref(desc)))
+
+
+def eval_ws_floats(kind, batch, pixels):
+    """mtt_eval_ws_floats for meter kind `kind` on `batch` images of `pixels` pixels"""
+    lib = load()
+    desc = EvalDesc()
+    desc.kind, desc.B, desc.HW = int(kind), int(batch), int(pixels)
+    return int(lib.mtt_eval_ws_floats(C.byref(desc)))
 
 
 def dtype_code(t):
@@ -439,7 +466,7 @@ def call(name, **kw):
             desc = st()
             extra = [(_addr(a) if isinstance(a, torch.Tensor) else a) for a in kw["xargs"]]
         else:
-            desc = (POSTPROC[name] if name in POSTPROC else DESCS[name])()
+            desc = (POSTPROC[name] if name in POSTPROC else EVAL[name] if name in EVAL else DESCS[name])()
         for k, v in kw.items():
             if k == "xargs":
                 continue
