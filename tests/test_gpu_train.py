@@ -342,6 +342,27 @@ def test_swin_training_path_checks_its_input_size():
 
 
 @pytest.mark.gpu
+def test_invpt_eval_pass_registers_no_second_pack_set():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import mtt_amd
+    from test_host_cpu import check_invpt_eval_pass_registers_no_second_pack_set
+    try:
+        check_invpt_eval_pass_registers_no_second_pack_set("cuda")
+    finally:
+        mtt_amd.ops.clear_pack_cache()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", ["x3", "x3f"])
+def test_invpt_one_forward_both_ways(prec):
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from test_host_cpu import check_invpt_one_forward_both_ways
+    check_invpt_one_forward_both_ways(prec, "cuda")
+
+
+@pytest.mark.gpu
 @pytest.mark.timeout(1500)
 def test_mixed_precision_training_trajectory_follows_the_fp32_reference_over_200_steps():
     """Does x3f TRAIN like the reference?  The reference trains in fp32 (no AMP); x3f = fp32-class forward + bf16

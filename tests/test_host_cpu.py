@@ -436,6 +436,88 @@ def test_invpt_training_gradients_on_emulator(emulated):
     assert any("scale_embed.2" in k for k in dead) and any("norm_mt." in k for k in dead)
 
 
+def _invpt_product(name, prec, device):
+    """-> (cfg, TransformerNet on `device` with the synthetic weights, a batch of two images)"""
+    cfg = configs.invpt(name)
+    model = conftest.build_product_model(cfg, prec, device)
+    contract = [(k, list(v.shape)) for k, v in model.state_dict().items()]
+    model.load_state_dict({k: v.to(device) for k, v in weights.synth_state_dict(contract, 0).items()}, strict=True)
+    return cfg, model, weights.synth_images(2, cfg["img_size"], 2).to(device)
+
+
+def _invpt_outputs(out):
+    return dict({t: v for t, v in out.items() if t != "inter_preds"}, **{"inter/" + t: v for t, v in out["inter_preds"].items()})
+
+
+def check_invpt_eval_pass_registers_no_second_pack_set(device):
+    """(shared with tests/test_gpu_train.py) InvPT's one forward takes its registry packs under the same tags and through the same pack
+    calls with and without gradients: an evaluation pass in front of a training step leaves exactly the registry entries the training step
+    alone leaves (the body of check_swin_eval_pass_registers_no_second_pack_set, on the whole TransformerNet)."""
+    import mtt_amd
+    import train_check
+    cfg, model, x = _invpt_product("mini8", "x3f", device)
+    train_check.skip_unless_own_pitch(cfg)
+
+    def train_pass():
+        model.train()
+        sum((v.float() * torch.linspace(-1, 1, v.numel(), device=v.device).view(v.shape)).sum() for v in _invpt_outputs(model(x)).values()).backward()
+
+    mtt_amd.ops.clear_pack_cache()
+    train_pass()
+    alone = set(mtt_amd.ops._packs)
+    mtt_amd.ops.clear_pack_cache()
+    model.eval()
+    with torch.no_grad():
+        model(x)
+    assert mtt_amd.ops._packs, "the evaluation pass builds packs of its own"
+    train_pass()
+    assert set(mtt_amd.ops._packs) == alone, sorted(map(str, set(mtt_amd.ops._packs) ^ alone))
+
+
+def test_invpt_eval_pass_registers_no_second_pack_set(emulated):
+    check_invpt_eval_pass_registers_no_second_pack_set("cpu")
+
+
+# Worst relative L2 difference, over the task outputs and inter_preds of mini8 in train mode (x3 and x3f), between the no-grad schedule and the
+# with-gradients schedule, measured on the commit BEFORE the two were one forward (it had both): CPU emulator 4.405e-06 (x3f; x3 1.43e-07),
+# MI355X 4.774e-06 (x3f; x3 1.67e-06).  The legs round in different places (the projections' output mapping, layernorm_mt, the skip add, the
+# head node), so zero is not expected; twice the larger value covers the box-to-box spread of a deterministic computation.
+INVPT_BOTH_WAYS_BOUND = 2 * 4.774e-06
+
+
+def check_invpt_one_forward_both_ways(prec, device):
+    """(shared with tests/test_gpu_train.py) mini8 in train mode, same weights and images: the one forward called under no_grad and with
+    gradients gives the same task outputs and inter_preds within INVPT_BOTH_WAYS_BOUND, and the no-grad call records no graph."""
+    import train_check
+    cfg, model, x = _invpt_product("mini8", prec, device)
+    train_check.skip_unless_own_pitch(cfg)
+    model.train()
+    with torch.no_grad():
+        plain = _invpt_outputs(model(x))
+    assert all(v.grad_fn is None and not v.requires_grad for v in plain.values())
+    kept = _invpt_outputs(model(x))
+    assert all(v.grad_fn is not None for v in kept.values())
+    for k, v in kept.items():
+        err = float((plain[k].double() - v.detach().double()).norm() / v.detach().double().norm())
+        print(f"invpt both ways {device} {prec} {k}: {err:.3e}")
+        assert err <= INVPT_BOTH_WAYS_BOUND, (k, err)
+
+
+@pytest.mark.parametrize("prec", ["x3", "x3f"])
+def test_invpt_one_forward_both_ways(emulated, prec):
+    check_invpt_one_forward_both_ways(prec, "cpu")
+
+
+def test_invpt_pitch_check_is_raised_with_gradients_only(emulated):
+    """mini's widths 40 / 20 / 10 are not their own pitch: only the backward kernels mind (invpt_autograd._check8)"""
+    cfg, model, x = _invpt_product("mini", "x3", "cpu")
+    model.train()
+    with torch.no_grad():
+        model(x)
+    with pytest.raises(NotImplementedError, match="own channel pitch"):
+        model(x)
+
+
 def test_training_gradients_with_forced_split_k(emulated, monkeypatch):
     """Same gradient check with the split-K weight-gradient path forced on (production uses it for >= 4096-row reductions)."""
     import mtt_amd
