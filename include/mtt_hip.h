@@ -134,6 +134,17 @@ typedef struct {
    * operand rounded to bf16, [M, ld_a16] — what the bf16 backward of that layer reads (weight gradient of the predictions).
    * a_scale == NULL: no prologue.  Other kernels return MTT_E_UNSUPPORTED when it is set. */
   const float* a_scale; const float* a_shift; int32_t a_act; void* a_aux16; int64_t ld_a16;
+  /* DropPath work skipping (optional; NULL = off, every kernel then behaves bit for bit as without these fields).  skip_scale is the [B, 2]
+   * DropPath table of the branch (the `rowscale` layout): table row r belongs to sample q = r / skip_mb and class c = (r % skip_mb) >=
+   * skip_prompt, and is DEAD iff skip_scale[2 q + c] == 0.0f.  The caller promises that dead rows only ever contribute exact zeros.
+   *   - gemm_ring3_kernel<false> / gemm_dma_kernel<1> (a_op = b_op = MTT_OP_K): table row = A row m.  A 256-row tile whose rows are all dead
+   *     skips its K loop and runs the unchanged epilogue on zero accumulators: it stores exactly what the call without skip_scale stores when
+   *     the dead rows of A (both planes) are zero — bias, activation, aux_out, rowscale, resid and the colsum partials included.
+   *   - skip_row0: for a_op = b_op = MTT_OP_R calls (weight gradients) reduction index k of batch member z is table row skip_row0 + z * K + k.
+   *     No kernel skips reduction steps yet (gemm_tn_kernel ignores the table: finding the kept steps cost its K loop more than the dead
+   *     steps saved); the field fixes the meaning for one that does.
+   * Other kernels ignore the fields. */
+  const float* skip_scale; int32_t skip_mb; int32_t skip_prompt; int64_t skip_row0;
 } mtt_gemm_desc;
 size_t mtt_gemm_colsum_ws_floats(const mtt_gemm_desc* d);
 
@@ -161,6 +172,14 @@ typedef struct {
   float scale;
   int32_t variant;   /* MTT_ATTN_* (0 = AUTO: the swapped-product flash kernel for bf16 storage, the plain kernel otherwise) */
   const void* qkv_lo; void* out_lo;   /* dtype == MTT_SPLIT (forward, MTT_PREC_X3): lo planes of qkv / out, same layout as the hi planes */
+  /* DropPath work skipping (optional, NULL = off): the branch's [B, 2] table as in mtt_gemm_desc with mb = N, n_prompt = T.  When
+   * skip_scale[2 b + 1] == 0 the patch rows of image b are dead: the caller promises dout == 0 there and reads neither out nor lse there.
+   *   forward (attn_fwd_x3_kernel, attn_fwd_fast_kernel<2>): a 128-row query block with qb * 128 >= T of such an image stores zeros to out
+   *     (both planes) and 0 to lse and stages nothing; block 0 (prompt rows, rawlog) always runs.
+   *   backward (VER 2 kernels): the same 128-row blocks store zero dq rows; the dK/dV kernel stops after its first ceil(T / 64) 64-row query
+   *     tiles — a superset of the forward's dead rows, so every tile it processes has a forward-written out and lse.  Both store what the
+   *     unskipped kernels store for dout == 0 there.  stat entries of skipped rows stay unwritten. */
+  const float* skip_scale;
 } mtt_attn_desc;
 int mtt_attn_fwd(const mtt_attn_desc* d, void* stream);
 /* Flash backward of mtt_attn_fwd (autograd of taskprompter.py:201-210 / vit.py:184-191), bf16 storage + MTT_PREC_BF16 only

@@ -57,13 +57,14 @@ class GemmDesc(C.Structure):
         ("A_lo", ptr), ("B_lo", ptr), ("D_lo", ptr),
         ("colsum_out", ptr), ("colsum_ws", ptr),
         ("a_scale", ptr), ("a_shift", ptr), ("a_act", i32), ("a_aux16", ptr), ("ld_a16", i64),
+        ("skip_scale", ptr), ("skip_mb", i32), ("skip_prompt", i32), ("skip_row0", i64),
     ]
 
 
 class AttnDesc(C.Structure):
     _fields_ = [("qkv", ptr), ("out", ptr), ("rawlog", ptr), ("lse", ptr),
                 ("B", i32), ("N", i32), ("nH", i32), ("T", i32), ("dtype", i32), ("prec", i32), ("scale", f32),
-                ("variant", i32), ("qkv_lo", ptr), ("out_lo", ptr)]
+                ("variant", i32), ("qkv_lo", ptr), ("out_lo", ptr), ("skip_scale", ptr)]
 
 
 class SoftmaxDesc(C.Structure):

@@ -210,6 +210,11 @@ def _enc_wgrad(dy, x, N, Kp, prec, bias=True):
     return _wgrad(dy, x, N, Kp, prec), db
 
 
+def _skip_kw(skip):
+    """(table, mb, n_prompt) | None -> the DropPath skip fields of mtt_gemm_desc"""
+    return {} if skip is None else dict(skip_scale=skip[0], skip_mb=skip[1], skip_prompt=skip[2])
+
+
 def _enc_dgrad(dy, weight, wpack2d, M, N_in, K_out, prec, out_dtype, tag, colsum=False, **epi):
     """dx = dy @ W.  bf16 mode: uses a cached transposed pack W^T [N_in, K_out] so that both operands are
     reduction-contiguous (fast GEMM path); otherwise the transposing B stager.  colsum=True -> (dx, column sums of dx as stored): with the
@@ -297,14 +302,16 @@ def attention_bwd(qkv, dao, drawlog, B, N, nH, T, prec):
 
 HEAD_DGRAD_DMA = True   # TaskHeadsFn: the prediction dgrad on the LDS-DMA kernel (tests / A-B runs set it to False)
 FLASH_BWD = True        # bf16: mtt_attn_bwd (tests set it to False to exercise the materialised batched-GEMM backward in bf16)
+DROP_SKIP = True        # the encoder's GEMMs and attention kernels get the branch's DropPath table and skip tiles of dropped rows (A/B: False)
 
 
-def attention_bwd_flash(qkv, ao, lse, dao, drawlog, B, N, nH, T, prec):
-    """bf16 mode: mtt_attn_bwd (recomputes P tile by tile from q, k and the forward's log-sum-exp; no N x N buffer)."""
+def attention_bwd_flash(qkv, ao, lse, dao, drawlog, B, N, nH, T, prec, skip_scale=None):
+    """bf16 mode: mtt_attn_bwd (recomputes P tile by tile from q, k and the forward's log-sum-exp; no N x N buffer).  skip_scale: the DropPath
+    table the forward ran under (dao is zero in its dead rows; ao and lse of the forward's dead blocks are not read)."""
     dqkv = torch.empty_like(qkv)
     dsum = torch.empty(B, nH, 2, (N + 3) // 4 * 4, dtype=torch.float32, device=qkv.device)      # rowsum(dO*O) and lse*log2e
     ops.call("attn_bwd", qkv=qkv, out=ao, rawlog=None, lse=lse, B=B, N=N, nH=nH, T=T, dtype=dtype_code(qkv), prec=prec.code,
-             scale=64 ** -0.5, xargs=[dao, drawlog, dqkv, dsum])
+             scale=64 ** -0.5, xargs=[dao, drawlog, dqkv, dsum], **({} if skip_scale is None else dict(skip_scale=skip_scale)))
     return dqkv
 
 
@@ -334,6 +341,9 @@ def attn_half(XT, g1, b1, eps, Wqkv, bqkv, Wproj, bproj, Wtt, btt, Wtt1, btt1, r
     chan = Wtt is not None
     split = prec.split                       # x3f: x3 products on pre-split planes (LDS-DMA kernel), bf16 backward on the hi planes
     odt = "split" if split else prec.adt     # storage dtype (a group override only changes operand rounding)
+    # DropPath skip: what this branch computes for a dropped row is multiplied by the table's zero in the proj epilogue, so the attention
+    # blocks and proj tiles made of dropped patch rows are not computed (the qkv GEMM stays whole: dropped rows still serve as keys / values)
+    skip = rowscale if DROP_SKIP else None
     xn, mean, rstd = ops.layernorm(XT, g1, b1, eps, prec, save_stats=keep, out_dtype=odt)
     wq = ops.pack_linear([Wqkv], pe, tag + ('qkv',), split=split)
     wp = ops.pack_linear([Wproj], pe, tag + ('proj',), split=split)
@@ -344,10 +354,10 @@ def attn_half(XT, g1, b1, eps, Wqkv, bqkv, Wproj, bproj, Wtt, btt, Wtt1, btt1, r
         ao16, rawlog, lse = ops.attention(q16, B, N, nH, T, pa)
         ao = ops.cast2d(ao16, ao16.shape[0], C, C, prec.adt, ldd=C)
     else:
-        ao, rawlog, lse = ops.attention(qkv, B, N, nH, T, pa, want_lse=flash)
+        ao, rawlog, lse = ops.attention(qkv, B, N, nH, T, pa, want_lse=flash, skip_scale=skip)
     XT2 = torch.empty_like(XT)
     rows = dict(d_rows=(N, N * C, C), M=B * N) if keep or rowscale is not None else {}
-    ops.linear(ao, wp, C, pe, bias=bproj[None], out=XT2, resid=XT, rowscale=rowscale, n_prompt=T, **rows)
+    ops.linear(ao, wp, C, pe, bias=bproj[None], out=XT2, resid=XT, rowscale=rowscale, n_prompt=T, skip=None if skip is None else (skip, N, T), **rows)
     cq = wt = wt1 = xp32 = rawchan = None
     if chan:                                 # channel attention: queries token_trans(norm1(prompts)), keys norm1(x)^T, windowed (:216-250)
         wt = ops.pack_linear([Wtt], ps, tag + ('tt',))
@@ -390,10 +400,12 @@ def mlp_half(XT2, g2, b2n, eps, W1, b1, W2, b2, rowscale, geo, prec, tag, *, kee
     # elements per block (GELU_DAUX: the derivative with the forward, round 6)
     z = torch.empty(B * N, Hd, dtype=prec.bwd.adt, device=XT2.device) if keep else None
     daux = keep and GELU_DAUX and z.dtype == torch.bfloat16
-    hmid = ops.linear(xn2, w1, Hd, pe, bias=b1[None], act=ACT_GELU_DAUX if daux else ACT_GELU, aux_out=z, out_dtype=odt)[0]
+    # DropPath skip: fc2's epilogue multiplies a dropped row by the table's zero, so row tiles made of dropped rows run neither GEMM's K loop
+    skip = (rowscale, N, T) if DROP_SKIP and rowscale is not None else None
+    hmid = ops.linear(xn2, w1, Hd, pe, bias=b1[None], act=ACT_GELU_DAUX if daux else ACT_GELU, aux_out=z, out_dtype=odt, skip=skip)[0]
     XT3 = torch.empty_like(XT2)
     rows = dict(d_rows=(N, N * C, C), M=B * N) if keep or rowscale is not None else {}
-    ops.linear(hmid, w2, C, pe, bias=b2[None], out=XT3, resid=XT2, rowscale=rowscale, n_prompt=T, **rows)
+    ops.linear(hmid, w2, C, pe, bias=b2[None], out=XT3, resid=XT2, rowscale=rowscale, n_prompt=T, skip=skip, **rows)
     saved = (XT2, g2, mean, rstd, ops._hi(xn2), z, ops._hi(hmid), ops._hi(w1), ops._hi(w2), rowscale) if keep else None
     return XT3, saved
 
@@ -431,11 +443,14 @@ class AttnHalfFn(Function):
         dXT2 = dXT2.contiguous()
         # ---- spatial attention ---------------------------------------------------------------------------------
         g, dbproj = _scaled_colsum(dXT2, rowscale, N, T, prec)
+        # DropPath skip: g is zero in the dropped rows, so are dao and (through dS = 0) their part of dqkv; ao / lse of the forward's
+        # skipped blocks are never read
+        skip = (rowscale, N, T) if DROP_SKIP and rowscale is not None else None
         dWproj, _ = _enc_wgrad(g, ao, C, C, prec, bias=False)
-        dao = _enc_dgrad(g, Wproj_, wp[0], M, C, C, prec, prec.adt, 'proj')
+        dao = _enc_dgrad(g, Wproj_, wp[0], M, C, C, prec, prec.adt, 'proj', **_skip_kw(skip))
         dl = drawlog.contiguous() if (T > 0 and drawlog is not None and drawlog.numel()) else None
         if lse is not None:
-            dqkv = attention_bwd_flash(qkv, ao, lse, dao, dl, B, N, nH, T, prec)
+            dqkv = attention_bwd_flash(qkv, ao, lse, dao, dl, B, N, nH, T, prec, skip_scale=skip and skip[0])
         else:
             dqkv = attention_bwd(qkv, dao, dl, B, N, nH, T, prec)
         dWqkv, dbqkv = _enc_wgrad(dqkv, xn, 3 * C, C, prec)
@@ -501,11 +516,13 @@ class MlpHalfFn(Function):
         dXT3 = dXT3.contiguous()
         g, db2 = _scaled_colsum(dXT3, rowscale, N, T, prec)
         W1_, W2_ = ctx.params
+        # DropPath skip: g, and with it dz, is zero in the dropped rows (the two input gradients; the weight gradients run whole)
+        skip = (rowscale, N, T) if DROP_SKIP and rowscale is not None else None
         dW2, _ = _enc_wgrad(g, hmid, C, Hd, prec, bias=False)
         dz, db1 = _enc_dgrad(g, W2_, w2[0], M, Hd, C, prec, prec.adt, 'fc2', colsum=True, act=ACT_MUL_AUX if ctx.daux else ACT_GELU_BWD, aux_in=z,
-                             aux_dtype=dtype_code(z), ldaux=Hd)
+                             aux_dtype=dtype_code(z), ldaux=Hd, **_skip_kw(skip))
         dW1, _ = _enc_wgrad(dz, xn2, Hd, C, prec, bias=False)
-        dxn2 = _enc_dgrad(dz, W1_, w1[0], M, C, Hd, prec, prec.adt, 'fc1')
+        dxn2 = _enc_dgrad(dz, W1_, w1[0], M, C, Hd, prec, prec.adt, 'fc1', **_skip_kw(skip))
         dXT2, dg2, dbn2 = _ln_bwd_join(dXT3, XT2, dxn2, g2, mean, rstd, ctx.eps)
         return dXT2, dg2, dbn2, None, dW1, db1, dW2, db2, None, None, None, None
 

@@ -41,7 +41,11 @@ struct BwdP {
   const bf16_t* qkv; const bf16_t* dout; const float* stat; const float* drawlog; bf16_t* dqkv;
   int B, N, nH, T, Np; float scale;
   const bf16_t* out; const float* lse; float* stat_w;   // MTT_ABWD_DQSTAT: the dQ kernel writes stat itself
+  const float* skip_scale;                              // mtt_attn_desc.skip_scale (VER 2 kernels; NULL = off)
 };
+
+// DropPath skip: are the patch rows of image b dead (dout == 0 there, out / lse possibly never written)?  Block-uniform, scalar unit.
+MTT_DEV bool bwd_patches_dead(const BwdP& p, int b) { return p.skip_scale != nullptr && p.skip_scale[2 * b + 1] == 0.0f; }
 
 // sum over one 8-element chunk of dO * O (packed bf16 pairs): the unit both producers of stat[.,.,0,.] add up in the same order
 MTT_DEV float dot8_bf16(const u32x4& a, const u32x4& g) {
@@ -156,6 +160,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
   const int li = lane & 15, lg = lane >> 4;
   const int64_t tok0 = (int64_t)b * N;
   const int64_t bh = (int64_t)b * p.nH + h;
+  if (VER == 2 && qb * 128 >= p.T && bwd_patches_dead(p, b)) {
+    // a block of dead patch rows (the blocks the forward skipped): dS = 0 for its rows, so dq = 0.  Its stat entries stay unwritten —
+    // the dK/dV kernel does not visit these rows — except the zero padding, which keeps its contract.  No barrier has been reached.
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int idx = tid + 256 * i, qrow = qb * 128 + (idx >> 3);
+      if (qrow < N) *(u32x4*)(p.dqkv + (tok0 + qrow) * 3 * C + h * HD + (idx & 7) * 8) = (u32x4){0u, 0u, 0u, 0u};
+    }
+    if (MTT_ABWD_DQSTAT && qb == nqb - 1 && tid < p.Np - N) {
+      p.stat_w[bh * 2 * p.Np + N + tid] = 0.f;
+      p.stat_w[bh * 2 * p.Np + p.Np + N + tid] = 0.f;
+    }
+    return;
+  }
   const int q0 = qb * 128 + wave * 32;
   const bool active = q0 < N;
 
@@ -594,8 +612,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
   const float sc2 = p.scale * LOG2E, inv_scale = 1.0f / p.scale;
 
   const int nq = (N + 63) / 64;
+  // DropPath skip (VER 2): with the image's patch rows dead, the query tiles past the prompt rows' (a suffix of the loop) carry dO = 0 and add
+  // nothing to dK / dV: only the trip count shrinks, to nlive tiles; the KIND of a tile still follows from the true N.  T == 0: no tile at all.
+  int nlive = nq;
+  if (VER == 2 && bwd_patches_dead(p, b)) { const int np = (p.T + 63) / 64; nlive = np < nq ? np : nq; }
   if (VER == 2) {
-    dma_issue(smem, smem + STAT_LDS, 0);
+    if (nlive > 0) dma_issue(smem, smem + STAT_LDS, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   } else {
     stage_load(0);
@@ -608,7 +630,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
   auto tile = [&](auto stage_tag, auto ragged_tag, auto first_tag, int j) {
     constexpr int ST = decltype(stage_tag)::value;
     constexpr int RG = decltype(ragged_tag)::value, FT = decltype(first_tag)::value;
-    const bool more = RG != 1 && j + 1 < nq;          // a tile known to be ragged at compile time is the last one
+    const bool more = RG != 1 && j + 1 < nlive;       // a tile known to be ragged at compile time is the last one
     if (more) {
       if (VER == 2) dma_issue(smem + (1 - ST) * STAGE, smem + STAT_LDS + (1 - ST) * STAT_STAGE, (j + 1) * 64);
       else stage_load((j + 1) * 64);
@@ -773,13 +795,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
   if (VER == 2 && MTT_ABWD_TILES) {
     // the first tile (drawlog add on its prompt rows) and the ragged last tile are peeled; the tiles between run the body without selects
     const int nfull = N / 64;
-    if (nfull >= 1) tile(BwdNo{}, BwdNo{}, BwdYes{}, 0);
-    else tile(BwdNo{}, BwdYes{}, BwdYes{}, 0);
-    for (int j = 1; j < nfull; j += 2) {
-      tile(BwdYes{}, BwdNo{}, BwdNo{}, j);
-      if (j + 1 < nfull) tile(BwdNo{}, BwdNo{}, BwdNo{}, j + 1);
+    const int nlf = nfull < nlive ? nfull : nlive;     // live full tiles
+    if (nlive >= 1) {
+      if (nfull >= 1) tile(BwdNo{}, BwdNo{}, BwdYes{}, 0);
+      else tile(BwdNo{}, BwdYes{}, BwdYes{}, 0);
     }
-    if (nfull >= 1 && nfull < nq) {
+    for (int j = 1; j < nlf; j += 2) {
+      tile(BwdYes{}, BwdNo{}, BwdNo{}, j);
+      if (j + 1 < nlf) tile(BwdNo{}, BwdNo{}, BwdNo{}, j + 1);
+    }
+    if (nfull >= 1 && nfull < nq && nlive == nq) {
       if (nfull & 1) tile(BwdYes{}, BwdYes{}, BwdNo{}, nfull);
       else tile(BwdNo{}, BwdYes{}, BwdNo{}, nfull);
     }
@@ -833,7 +858,7 @@ extern "C" int mtt_attn_bwd(const mtt_attn_desc* d, const void* dout, const floa
     hipLaunchKernelGGL(attn_stat_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, (const bf16_t*)d->out, (const bf16_t*)dout,
                        d->lse, stat, d->B, d->N, d->nH, Np);
   BwdP p{(const bf16_t*)d->qkv, (const bf16_t*)dout, stat, d->T > 0 ? drawlog : nullptr, (bf16_t*)dqkv, d->B, d->N, d->nH, d->T, Np, d->scale,
-         (const bf16_t*)d->out, d->lse, stat};
+         (const bf16_t*)d->out, d->lse, stat, d->skip_scale};
   dim3 grid((unsigned)(((d->N + 127) / 128) * d->nH * d->B));
   if (ver == 0) {
     hipLaunchKernelGGL(attn_bwd_dq_kernel<0>, grid, dim3(256), smem_dq, s, p);

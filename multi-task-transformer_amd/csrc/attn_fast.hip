@@ -39,6 +39,25 @@ MTT_DEV void attn_glds16(const bf16_t* src, unsigned char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
+// DropPath skip (mtt_attn_desc.skip_scale): is query block qb of image b made of dead patch rows only?  Block-uniform (scalar unit).
+MTT_DEV bool attn_block_dead(const mtt_attn_desc& d, int b, int qb) {
+  return d.skip_scale != nullptr && qb * 128 >= d.T && d.skip_scale[2 * b + 1] == 0.0f;
+}
+// ... then the block stores zeros to its rows of out (and out_lo) and 0 to lse — the workgroup's 256 threads cover 128 rows x 128 bytes of
+// the head's columns as 16-byte chunks — and returns before any barrier or LDS-DMA issue.
+MTT_DEV void attn_store_dead_block(const mtt_attn_desc& d, int b, int h, int qb) {
+  const int N = d.N, C = d.nH * HD, tid = threadIdx.x;
+  const u32x4 z = (u32x4){0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int idx = tid + 256 * i, qrow = qb * 128 + (idx >> 3);
+    if (qrow >= N) continue;
+    const int64_t oi = ((int64_t)b * N + qrow) * C + h * HD + (idx & 7) * 8;
+    *(u32x4*)((bf16_t*)d.out + oi) = z;
+    if (d.out_lo) *(u32x4*)((bf16_t*)d.out_lo + oi) = z;
+  }
+  if (d.lse && tid < 128 && qb * 128 + tid < N) d.lse[((int64_t)b * d.nH + h) * N + qb * 128 + tid] = 0.f;
+}
 template <int OFF>
 MTT_DEV u32x2 attn_ds_read_tr16(unsigned addr) {
   u32x2 r;
@@ -67,6 +86,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_fast_kernel(const AttnP p) {
   const int wi = xcd_remap(blockIdx.x, gridDim.x);
   const int qb = wi % nqb, bh = wi / nqb;
   const int h = bh % d.nH, b = bh / d.nH;
+  if (VER == 2 && attn_block_dead(d, b, qb)) { attn_store_dead_block(d, b, h, qb); return; }
   const int N = d.N, C = d.nH * HD;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lg = lane >> 4;
@@ -426,6 +446,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3_kernel(const AttnP p) {
   const int wi = xcd_remap(blockIdx.x, gridDim.x);
   const int qb = wi % nqb, bh = wi / nqb;
   const int h = bh % d.nH, b = bh / d.nH;
+  if (attn_block_dead(d, b, qb)) { attn_store_dead_block(d, b, h, qb); return; }
   const int N = d.N, C = d.nH * HD;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lg = lane >> 4;

@@ -26,6 +26,7 @@ struct GemmP {
   FastDiv divW, divH, divCp, div3;   // conv geometry
   FastDiv divAmb, divDmb, divRmb;    // row-group mappings
   FastDiv divPsW, divPsH, divPsCo;   // pixel-shuffle store
+  FastDiv divSkip;                   // DropPath table rows -> sample (skip_mb)
   int tiles_m, tiles_n;
   int group_m;
 #ifdef MTT_GEMM_TRACE
@@ -55,6 +56,22 @@ MTT_DEV int64_t row_off(uint32_t m, int mb, int64_t bs, int64_t ld, FastDiv f) {
   if (mb <= 0) return (int64_t)m * ld;
   const uint32_t q = fdiv(m, f);
   return (int64_t)q * bs + (int64_t)(m - q * (uint32_t)mb) * ld;
+}
+
+// DropPath work skipping (mtt_gemm_desc.skip_scale): are the table rows [r0, r1) all dead?  Walks the (sample, class) segments the range
+// touches — at most four for a 256-row tile when skip_mb >= 256, a short loop otherwise.  r0 / r1 are workgroup-uniform, so the walk and
+// its table reads run on the scalar unit.  The host guarantees skip_mb > 0 and 0 <= skip_prompt <= skip_mb.
+MTT_DEV bool skip_rows_dead(const GemmP& p, uint32_t r0, uint32_t r1) {
+  const uint32_t mb = (uint32_t)p.d.skip_mb, np = (uint32_t)p.d.skip_prompt;
+  uint32_t q = fdiv(r0, p.divSkip);
+  uint32_t o = r0 - q * mb;                          // offset of r0 inside its sample
+  for (uint32_t r = r0; r < r1;) {
+    const uint32_t c = o >= np ? 1u : 0u;
+    if (p.d.skip_scale[2 * q + c] != 0.0f) return false;
+    if (c) { r += mb - o; ++q; o = 0; }              // on to the next sample's prompt rows (an empty segment when skip_prompt == 0)
+    else { r += np - o; o = np; if (np == mb) { ++q; o = 0; } }   // (a sample without patch rows: straight to the next one)
+  }
+  return true;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -807,6 +824,10 @@ __global__ __launch_bounds__(512, 1) void gemm_dma_kernel(const GemmP p) {
   const int m0 = tile_m * BM2, n0 = tile_n * 256;
   const int z = blockIdx.z;
   const int zo = z / p.d.batch_inner, zi = z - zo * p.d.batch_inner;
+  // DropPath skip (ADDR 1, workgroup-uniform): a tile whose A rows are all dead stages nothing and runs no K step — every wave still passes
+  // the same barriers — and enters the epilogue with zero accumulators
+  const bool dead = ADDR == 1 && p.d.skip_scale != nullptr &&
+                    skip_rows_dead(p, (uint32_t)m0, (uint32_t)(m0 + BM2 < p.d.M ? m0 + BM2 : p.d.M));
   const int64_t za = (int64_t)zo * p.d.a_zo + (int64_t)zi * p.d.a_zi, zb = (int64_t)zo * p.d.b_zo + (int64_t)zi * p.d.b_zi;
   const bf16_t* Abase = (const bf16_t*)p.d.A + za;
   const bf16_t* Bbase = (const bf16_t*)p.d.B + zb;
@@ -882,8 +903,8 @@ __global__ __launch_bounds__(512, 1) void gemm_dma_kernel(const GemmP p) {
 #pragma unroll
     for (int b = 0; b < NT; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  const int nk = X3CAT ? 3 * (K / BK) : (K + BK - 1) / BK;
-  issue(0, 0);
+  const int nk = dead ? 0 : X3CAT ? 3 * (K / BK) : (K + BK - 1) / BK;
+  if (!dead) issue(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                    // tile 0 is in LDS
   MTT_TRACE(2);
@@ -999,7 +1020,7 @@ MTT_DEV void wait_vmcnt_dyn(int n) {
 template <int N_> MTT_DEV void wait_vmcnt_imm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N_) : "memory"); }
 
 template <bool CONV, bool EDGE>
-MTT_DEV void ring3_tile(const GemmP& p, unsigned char* smem, int m0, int n0, int zo, int zi) {
+MTT_DEV void ring3_tile(const GemmP& p, unsigned char* smem, int m0, int n0, int zo, int zi, bool dead) {
   constexpr int WAVES_N = EDGE ? 2 : 4, WAVES_M = EDGE ? 4 : 2, MT = EDGE ? 4 : 8, NT = 4;
   constexpr int NA = 2, NB = EDGE ? 1 : 2;                           // LDS-DMA pieces a wave issues per A / B part
   constexpr int PART = 256 * 64, SLOT = 4 * PART;                    // parts of a slot: 0 Ah, 1 Bh, 2 Bl, 3 Al
@@ -1013,7 +1034,7 @@ MTT_DEV void ring3_tile(const GemmP& p, unsigned char* smem, int m0, int n0, int
   const int li = lane & 15, lg = lane >> 4;
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
   const int late = wave >> 2;
-  const int nk = p.d.K >> 5;
+  const int nk = dead ? 0 : p.d.K >> 5;             // dead (DropPath skip, workgroup-uniform): no staging, no K step, the same barriers
 
   uint32_t aoff32[2], boff32[2];
   unsigned tapmask[2] = {0x1ffu, 0x1ffu};                            // CONV: bit t set <=> tap t of this lane's output pixel reads inside the image
@@ -1082,8 +1103,10 @@ MTT_DEV void ring3_tile(const GemmP& p, unsigned char* smem, int m0, int n0, int
   // counted waits (pieces issued AFTER the awaited part, see the header): steady state and the two last steps
   constexpr int W_BL = 3 * NA + 2 * NB, W_AL = 3 * NA + 3 * NB, W_AB = 2 * NA + 3 * NB;
   // prologue: (Ah Bh, Bl, Al)(0), (Ah Bh, Bl)(1)      [nk >= 2: the host requires K % 32 == 0 and K >= 64]
-  issue_part(0, 0); issue_part(0, 1); issue_part(0, 2); issue_part(0, 3);
-  issue_part(1, 0); issue_part(1, 1); issue_part(1, 2);
+  if (!dead) {
+    issue_part(0, 0); issue_part(0, 1); issue_part(0, 2); issue_part(0, 3);
+    issue_part(1, 0); issue_part(1, 1); issue_part(1, 2);
+  }
   wait_vmcnt_imm<2 * NA + 3 * NB>();                     // Ah, Bh of step 0 landed (this wave's pieces)
   __builtin_amdgcn_s_barrier();
   if (late) __builtin_amdgcn_s_barrier();
@@ -1169,8 +1192,11 @@ __global__ __launch_bounds__(512, 1) void gemm_ring3_kernel(const GemmP p) {
   const int zo = z / p.d.batch_inner, zi = z - zo * p.d.batch_inner;
   // workgroup-uniform: the columns this tile computes or zero-fills (n_store: the channel padding of the output pitch)
   const int ncols = (p.d.n_store > p.d.N ? p.d.n_store : p.d.N) - n0;
-  if (MTT_R3_EDGE && ncols <= 128 && p.d.store_mode == MTT_STORE_ROWS) ring3_tile<CONV, true>(p, smem, m0, n0, zo, zi);
-  else ring3_tile<CONV, false>(p, smem, m0, n0, zo, zi);
+  // DropPath skip (plain form only): all A rows of this tile dead -> zero accumulators into the unchanged epilogue
+  const bool dead = !CONV && p.d.skip_scale != nullptr &&
+                    skip_rows_dead(p, (uint32_t)m0, (uint32_t)(m0 + BM2 < p.d.M ? m0 + BM2 : p.d.M));
+  if (MTT_R3_EDGE && ncols <= 128 && p.d.store_mode == MTT_STORE_ROWS) ring3_tile<CONV, true>(p, smem, m0, n0, zo, zi, dead);
+  else ring3_tile<CONV, false>(p, smem, m0, n0, zo, zi, dead);
 }
 
 template <bool CONV>
@@ -1964,6 +1990,10 @@ extern "C" int mtt_gemm(const mtt_gemm_desc* dd, void* stream) {
   p.divRmb = make_div(d.r_mb > 0 ? d.r_mb : 1);
   p.divPsW = make_div(d.ps_W > 0 ? d.ps_W : 1); p.divPsH = make_div(d.ps_H > 0 ? d.ps_H : 1);
   p.divPsCo = make_div(d.ps_Co > 0 ? d.ps_Co : 1);
+  if (d.skip_scale) {                                   // DropPath table: classes inside a sample
+    if (d.skip_mb <= 0 || d.skip_prompt < 0 || d.skip_prompt > d.skip_mb || d.skip_row0 < 0) return MTT_E_BADARG;
+  }
+  p.divSkip = make_div(d.skip_scale ? d.skip_mb : 1);
   p.tiles_m = (d.M + BM - 1) / BM; p.tiles_n = (d.N + BN - 1) / BN;
   p.group_m = MTT_GROUP_M;
 #ifdef MTT_GEMM_TRACE

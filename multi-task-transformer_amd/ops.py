@@ -509,7 +509,7 @@ def stack_vec(vs, tag):
 # ---------------------------------------------------------------------------------------------
 def linear(x, wpack, N, prec, *, bias=None, act=ACT_NONE, out=None, out_dtype=None, M=None,
            a_rows=None, d_rows=None, resid=None, r_rows=None, rowscale=None, n_prompt=0, aux_out=None, aux_in=None,
-           colscale=None, alpha=1.0, batch_inner=1, d_z=None, ldd=None, n_store=None, a_affine=None):
+           colscale=None, alpha=1.0, batch_inner=1, d_z=None, ldd=None, n_store=None, a_affine=None, skip=None):
     """out[z] = epi(x[z] @ wpack[z]^T)  (mtt_gemm, both operands reduction-contiguous).
 
     x: [Z, M, lda] / [M, lda] (broadcast over Z) — or, with a_rows=(mb, bs, ld), any view whose first
@@ -517,7 +517,8 @@ def linear(x, wpack, N, prec, *, bias=None, act=ACT_NONE, out=None, out_dtype=No
     out: None -> new [Z, M, pitch(N)] in `out_dtype` (default activation dtype); else a tensor / base view
     addressed by d_rows=(mb, bs, ld) or, for a 3-D `out`, its own strides; d_z=(zo, zi) overrides the
     per-batch offsets of D (z = zo*batch_inner + zi).  resid fp32 is added in the epilogue (r_rows mapping,
-    default = D's); may alias `out`."""
+    default = D's); may alias `out`.  skip = (table [B, 2], mb, n_prompt): the DropPath table whose zero entries mark DEAD rows of x
+    (mtt_gemm_desc.skip_scale) — row tiles made of dead rows only skip their K loop; the caller multiplies those rows' results by zero."""
     Z, Nw, Kp = wpack.shape
     assert N <= Nw
     x_split = isinstance(x, Split)
@@ -578,6 +579,8 @@ def linear(x, wpack, N, prec, *, bias=None, act=ACT_NONE, out=None, out_dtype=No
         az = aux.stride(0) if aux.dim() == 3 else 0
         kw.update(aux_out=aux_out, aux_in=aux_in, aux_dtype=dtype_code(aux), ldaux=aux.shape[-1],
                   aux_zo=az * batch_inner, aux_zi=az if batch_inner > 1 else 0)
+    if skip is not None:
+        kw.update(skip_scale=skip[0], skip_mb=skip[1], skip_prompt=skip[2])
     if a_affine is not None:          # (scale [K], shift [K], act, bf16 side copy or None): the A prologue of the exact-fp32 tall GEMM (head_prologue_ok)
         sc, sh, a_act, a16 = a_affine
         kw.update(a_scale=sc, a_shift=sh, a_act=a_act, a_aux16=a16, ld_a16=a16.stride(-2) if a16 is not None else 0)
@@ -723,14 +726,17 @@ def layernorm(x, gamma, beta, eps, prec, save_stats=False, out_dtype=None, want3
     return ((y, y32) if want32 else y), mean, rstd
 
 
-def attention(qkv, B, N, nH, T, prec, want_lse=False):
-    """qkv [B*N, 3*nH*64] -> (out [B*N, nH*64], rawlog fp32 [B, nH, T, N] or None, lse or None)."""
+def attention(qkv, B, N, nH, T, prec, want_lse=False, skip_scale=None):
+    """qkv [B*N, 3*nH*64] -> (out [B*N, nH*64], rawlog fp32 [B, nH, T, N] or None, lse or None).  skip_scale: the branch's [B, 2] DropPath
+    table (mtt_attn_desc.skip_scale) — query blocks of dead patch rows store zeros (out, lse) instead of being computed."""
     C = nH * 64
     split = isinstance(qkv, Split)
     out = Split.empty((B * N, C), qkv.device) if split else torch.empty(B * N, C, dtype=qkv.dtype, device=qkv.device)
     rawlog = torch.empty(B, nH, T, N, dtype=torch.float32, device=qkv.device) if T > 0 else None
     lse = torch.empty(B, nH, N, dtype=torch.float32, device=qkv.device) if want_lse else None
     kw = dict(qkv_lo=qkv.lo, out_lo=out.lo) if split else {}
+    if skip_scale is not None:
+        kw.update(skip_scale=skip_scale)
     call("attn_fwd", qkv=_hi(qkv), out=_hi(out), rawlog=rawlog, lse=lse, B=B, N=N, nH=nH, T=T,
          dtype=dtype_code(qkv), prec=prec.code, scale=64 ** -0.5, **kw)
     return out, rawlog, lse
