@@ -4,6 +4,15 @@ mtt_adam_step), and the reference's polynomial learning-rate schedule.
 
 `FusedClipAdam` keeps torch.optim.Adam's state layout (`step`, `exp_avg`, `exp_avg_sq` per parameter), so a reference
 checkpoint's optimizer state loads with `load_state_dict` and vice versa.
+
+Precision of the hyper-parameters.  The descriptor (`mtt_adam_desc`) holds `beta1`, `beta2`, `eps`, `weight_decay` and `max_norm` as
+fp32, and the kernel forms `1 - beta` from the ROUNDED beta.  fp32(0.999) = 0.99900001287, so the kernel's 1 - beta2 is 0.00099998713:
+-1.29e-5 relative to 0.001, and every gradient-squared term enters `exp_avg_sq` smaller by that factor than in a torch.optim.Adam that
+keeps the betas as doubles (beta1 = 0.9: +2.4e-7 on 1 - beta1).  The bias corrections (`lr / (1 - beta1^t)`, `1 / sqrt(1 - beta2^t)`) are
+computed on the host from the UNROUNDED betas, exactly as torch does, and rounded to fp32 once.  The effect is therefore largest in the
+first steps, where `exp_avg_sq` consists of new terms only: the bias-corrected second moment is 1.3e-5 low, the step 6.5e-6 long; as the
+moment fills, its steady state sum (1 - b) * b^k * g^2 loses the dependence on the rounding of b to first order.  tests/optim_ref.py judges
+the kernels against an fp64 Adam on the descriptor's own (rounded) values; oracle/abi_emul.py rounds them the same way.
 """
 import math
 
@@ -15,7 +24,14 @@ from . import ops
 
 class FusedClipAdam(torch.optim.Optimizer):
     """Adam (torch.optim.Adam semantics: L2 weight decay added to the gradient, bias-corrected moments, no amsgrad) preceded by
-    global-norm gradient clipping.  `step()` returns the total gradient norm before clipping (like clip_grad_norm_)."""
+    global-norm gradient clipping.  `step()` returns the total gradient norm before clipping (like clip_grad_norm_).
+
+    Non-finite gradients.  A NaN (or infinite) gradient element makes the returned norm non-finite: check it (`torch.isfinite`) to detect a
+    diverged step.  The update itself differs from torch here: clip_grad_norm_ multiplies EVERY gradient by max_norm / (NaN + 1e-6) = NaN,
+    so one NaN element turns all parameters and moments NaN; the kernel's clamp `coef < 1 ? coef : 1` is false for a NaN coefficient and
+    yields coef = 1, so only the elements whose own gradient is NaN become NaN (in the parameter and both moments), and every other element
+    takes an UNCLIPPED Adam step (with an infinite norm coef is 0: finite gradients are ignored, 0 * inf is NaN in the infinite ones).  Neither is a
+    usable step; the norm is what tells the caller (tests/test_gpu_optim.py)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=0.0, capturable=False):
         """capturable=True: the step-dependent scalars (lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)) are read by the kernel from a device

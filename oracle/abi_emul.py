@@ -888,18 +888,22 @@ def adam_step(**kw):
     import numpy as np
     grads, params, ms, vs, numel = _adam_tables(kw)
     total = kw["xargs"][0]
+    # the descriptor's scalars are fp32 fields: the kernel sees the ROUNDED values, and forms 1 - beta from the rounded beta
+    # (beta2 = 0.999: 1 - beta2 = 0.00099998713, -1.29e-5 relative to 0.001)
+    f32 = lambda x: float(np.float32(x))
+    max_norm, beta1, beta2, eps, wd = (f32(kw[k]) for k in ("max_norm", "beta1", "beta2", "eps", "weight_decay"))
     coef = 1.0
-    if kw["max_norm"] > 0 and total is not None:
-        coef = min(1.0, kw["max_norm"] / (float(_rd(total, torch.arange(1))[0]) ** 0.5 + 1e-6))
-    step_size, inv_sqrt_bc2 = float(np.float32(kw["step_size"])), float(np.float32(kw["inv_sqrt_bc2"]))      # f32 descriptor fields
+    if max_norm > 0 and total is not None:
+        coef = min(1.0, max_norm / (float(_rd(total, torch.arange(1))[0]) ** 0.5 + 1e-6))
+    step_size, inv_sqrt_bc2 = f32(kw["step_size"]), f32(kw["inv_sqrt_bc2"])
     if kw.get("hyper") is not None:                      # device pair that replaces the by-value fields (graph-capturable step)
         step_size, inv_sqrt_bc2 = (float(v) for v in _rd(kw["hyper"], torch.arange(2)))
     for g, p, m, v, n in zip(grads, params, ms, vs, numel):
         ga, pa, ma, va = (_raw_f32(a, n) for a in (g, p, m, v))
-        gg = ga.astype("float64") * coef + kw["weight_decay"] * pa.astype("float64")
-        mm = kw["beta1"] * ma.astype("float64") + (1 - kw["beta1"]) * gg
-        vv = kw["beta2"] * va.astype("float64") + (1 - kw["beta2"]) * gg * gg
-        pa[:] = (pa.astype("float64") - step_size * mm / (np.sqrt(vv) * inv_sqrt_bc2 + kw["eps"])).astype("float32")
+        gg = ga.astype("float64") * coef + wd * pa.astype("float64")
+        mm = beta1 * ma.astype("float64") + (1 - beta1) * gg
+        vv = beta2 * va.astype("float64") + (1 - beta2) * gg * gg
+        pa[:] = (pa.astype("float64") - step_size * mm / (np.sqrt(vv) * inv_sqrt_bc2 + eps)).astype("float32")
         ma[:] = mm.astype("float32")
         va[:] = vv.astype("float32")
 

@@ -1388,8 +1388,8 @@ def iou3d_cases():
 
 # entry points the parity cases above do not run, and the test that checks each of them on the device instead
 COVERED_ELSEWHERE = {
-    "adam_step": "tests/test_gpu_train.py::test_fused_clip_adam_matches_torch_on_gpu",
-    "grad_sqnorm": "tests/test_gpu_train.py::test_fused_clip_adam_matches_torch_on_gpu",
+    "adam_step": "tests/test_gpu_optim.py::test_adam_step_case",
+    "grad_sqnorm": "tests/test_gpu_optim.py::test_grad_sqnorm_case",
     "segcopy": "tests/test_gpu_ops.py::test_segcopy_packs_refresh_and_gradient_scatter_on_device",
     "fcos3d_targets": "tests/test_gpu_fcos3d.py::test_targets_match_the_reference_fixture",
     "fcos3d_loss_fwd": "tests/test_gpu_fcos3d.py::test_losses_and_gradients_match_the_reference_fixture",
