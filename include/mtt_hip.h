@@ -65,9 +65,10 @@ enum { MTT_GEMM_AUTO = 0,
        MTT_GEMM_DMA256 = 3            /* the 256 x 256 LDS-DMA kernel (or, for two MTT_OP_R operands, the token-major weight-gradient kernel) on any shape it supports */,
        MTT_GEMM_DMA128 = 4            /* the 128 x 128 LDS-DMA kernel (K-contiguous bf16 operands; narrow or mid-size outputs) */,
        MTT_GEMM_GENERAL_EPILOGUE = 11 /* policy kernel, but always the general (run-time configured) epilogue: A/B of the specialised one */ };
-enum { MTT_ATTN_AUTO = 0, MTT_ATTN_PLAIN = 1,
-       MTT_ATTN_FAST_V0 = 2 /* A/B: the first flash kernels (run-time LDS stage, predicated register staging) */,
-       MTT_ATTN_FAST_V1 = 3 /* A/B: register-staged tiles, unrolled stages (AUTO = LDS-DMA staging + transpose reads) */ };
+/* mtt_attn_desc.variant: PLAIN forces the straightforward forward kernel; every other value takes the policy's kernel (the flash kernel
+ * for bf16 storage).  Values 2 and 3 once named two register-staged generations of the flash kernels (A/B only); they were removed
+ * without a change to the descriptor layout, the entry points or MTT_ABI_VERSION, and now mean what every unnamed value means. */
+enum { MTT_ATTN_AUTO = 0, MTT_ATTN_PLAIN = 1 };
 
 /* 3x3 (dilated) "same" convolution geometry for MTT_OP_CONV_* operands; stride 1, pad = dil. */
 typedef struct {
@@ -174,9 +175,9 @@ typedef struct {
   const void* qkv_lo; void* out_lo;   /* dtype == MTT_SPLIT (forward, MTT_PREC_X3): lo planes of qkv / out, same layout as the hi planes */
   /* DropPath work skipping (optional, NULL = off): the branch's [B, 2] table as in mtt_gemm_desc with mb = N, n_prompt = T.  When
    * skip_scale[2 b + 1] == 0 the patch rows of image b are dead: the caller promises dout == 0 there and reads neither out nor lse there.
-   *   forward (attn_fwd_x3_kernel, attn_fwd_fast_kernel<2>): a 128-row query block with qb * 128 >= T of such an image stores zeros to out
+   *   forward (attn_fwd_x3_kernel, attn_fwd_fast_kernel): a 128-row query block with qb * 128 >= T of such an image stores zeros to out
    *     (both planes) and 0 to lse and stages nothing; block 0 (prompt rows, rawlog) always runs.
-   *   backward (VER 2 kernels): the same 128-row blocks store zero dq rows; the dK/dV kernel stops after its first ceil(T / 64) 64-row query
+   *   backward (attn_bwd_dq_kernel, attn_bwd_dkv_kernel): the same 128-row blocks store zero dq rows; the dK/dV kernel stops after its first ceil(T / 64) 64-row query
    *     tiles — a superset of the forward's dead rows, so every tile it processes has a forward-written out and lse.  Both store what the
    *     unskipped kernels store for dout == 0 there.  stat entries of skipped rows stay unwritten. */
   const float* skip_scale;

@@ -2,34 +2,27 @@
 // tile by tile from q, k and the forward's log-sum-exp; nothing of size N x N reaches HBM and no atomics are used: two
 // kernels own disjoint outputs.  Both use the "swapped product" form of attn_fast.hip: a score tile comes out of the MFMA
 // in the C layout that IS the B fragment of the next product (reduction index permuted consistently on the A side, whose
-// fragments are two 8-byte reads of a transposed LDS tile), so P and dS never go through LDS.
+// fragments are two 8-byte transpose reads of the row-major LDS tile), so P and dS never go through LDS.
 //
-//   stat[b,h,0,i] = sum_d dO[i,d] * O[i,d],  stat[b,h,1,i] = lse[i] * log2(e)                (VER 2: written by the dQ kernel for its own
-//                 128 rows, in attn_stat_kernel's summation order; VER 0 / VER 1: attn_stat_kernel)
+//   stat[b,h,0,i] = sum_d dO[i,d] * O[i,d],  stat[b,h,1,i] = lse[i] * log2(e)                (written by the dQ kernel for its own 128
+//                 rows, read by the dK/dV kernel launched behind it on the same stream)
 //   dQ kernel : workgroup = 128 query rows (32 per wave, B fragments of Q and dO in registers); per 64-key tile
 //                 S^T = K Q^T, dP^T = V dO^T, dS^T = P^T o (dP^T - D),   dQ^T += K^T dS^T
 //   dKV kernel: workgroup = 128 keys (32 per wave, B fragments of K and V in registers); per 64-query tile
 //                 S = Q K^T, dP = dO V^T,   dV^T += dO^T P,   dK^T += Q^T dS
 // The softmax scale is applied once to the dQ / dK accumulators; drawlog (gradient of the forward's UNSCALED prompt-row
 // logits) is therefore added to dS divided by the scale.
+//
+// Three choices that each won an A/B against its plainer form (profiles/r09_attn_bwd_tiles_ab.log):
+//   * the tile kind (full / ragged, with / without the drawlog add) is a compile-time argument of tile(); interior tiles run a body
+//     without any end-of-sequence select;
+//   * the dK/dV kernel's per-row D and lse*log2(e) values travel with the Q / dO tile by LDS-DMA (no ordinary global load, hence no
+//     compiler-placed vmcnt(0), while the next tile's DMA is in flight);
+//   * the dQ kernel computes D for its 128 rows and writes both stat rows (no separate statistics kernel).
+// Two register-staged generations of both kernels (a transposed copy of each tile staged in LDS) and the plainer forms last existed at
+// commit f779e8e; these kernels matched the register-staged ones bit for bit on the shapes of tests/golden/attn_bitwise.json.
 #include "mtt_device.h"
 #include <type_traits>
-
-// A/B switches of the VER 2 kernels (-D...=0 through _build.build_variant restores the earlier form of one piece; VER 0 / VER 1 ignore them):
-//   MTT_ABWD_TILES  : the tile kind (full / ragged, with / without the drawlog add) is a compile-time argument of tile(); interior tiles
-//                     run a body without any end-of-sequence select
-//   MTT_ABWD_STATDMA: the dK/dV kernel's per-row D and lse*log2(e) values travel with the Q / dO tile by LDS-DMA (no ordinary global load,
-//                     hence no compiler-placed vmcnt(0), while the next tile's DMA is in flight)
-//   MTT_ABWD_DQSTAT : the dQ kernel computes D for its 128 rows and writes both stat rows; attn_stat_kernel is not launched
-#ifndef MTT_ABWD_TILES
-#define MTT_ABWD_TILES 1
-#endif
-#ifndef MTT_ABWD_STATDMA
-#define MTT_ABWD_STATDMA 1
-#endif
-#ifndef MTT_ABWD_DQSTAT
-#define MTT_ABWD_DQSTAT 1
-#endif
 
 namespace {
 
@@ -38,16 +31,17 @@ constexpr int KTILE = 64 * HD * 2;   // 8 KiB per bf16 tile
 constexpr float LOG2E = 1.4426950408889634f;
 
 struct BwdP {
-  const bf16_t* qkv; const bf16_t* dout; const float* stat; const float* drawlog; bf16_t* dqkv;
+  const bf16_t* qkv; const bf16_t* dout; float* stat; const float* drawlog; bf16_t* dqkv;   // stat: the dQ kernel writes it, dK/dV reads it
   int B, N, nH, T, Np; float scale;
-  const bf16_t* out; const float* lse; float* stat_w;   // MTT_ABWD_DQSTAT: the dQ kernel writes stat itself
-  const float* skip_scale;                              // mtt_attn_desc.skip_scale (VER 2 kernels; NULL = off)
+  const bf16_t* out; const float* lse;
+  const float* skip_scale;                              // mtt_attn_desc.skip_scale (NULL = off)
 };
 
 // DropPath skip: are the patch rows of image b dead (dout == 0 there, out / lse possibly never written)?  Block-uniform, scalar unit.
 MTT_DEV bool bwd_patches_dead(const BwdP& p, int b) { return p.skip_scale != nullptr && p.skip_scale[2 * b + 1] == 0.0f; }
 
-// sum over one 8-element chunk of dO * O (packed bf16 pairs): the unit both producers of stat[.,.,0,.] add up in the same order
+// sum over one 8-element chunk of dO * O (packed bf16 pairs): the unit of the summation order of stat[.,.,0,.], which the dQ kernel fixes
+// (within a chunk: the four pairs in order, lo * lo + hi * hi each; then the pairwise tree over the head's eight chunks there)
 MTT_DEV float dot8_bf16(const u32x4& a, const u32x4& g) {
   float s = 0.f;
 #pragma unroll
@@ -55,53 +49,9 @@ MTT_DEV float dot8_bf16(const u32x4& a, const u32x4& g) {
   return s;
 }
 
-__global__ __launch_bounds__(256) void attn_stat_kernel(const bf16_t* out, const bf16_t* dout, const float* lse, float* stat, int B, int N,
-                                                        int nH, int Np) {
-  const int C8 = nH * 8;
-  const int64_t total = (int64_t)B * N * C8;
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  float s = 0.f;
-  if (t < total) {
-    const u32x4 a = *(const u32x4*)(out + t * 8), g = *(const u32x4*)(dout + t * 8);
-    s = dot8_bf16(a, g);
-  }
-  s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
-  if (t < total && (threadIdx.x & 7) == 0) {
-    const int64_t tok = t / C8;
-    const int h = (int)(t % C8) >> 3;
-    const int b = (int)(tok / N), n = (int)(tok % N);
-    float* row = stat + ((int64_t)b * nH + h) * 2 * Np;
-    row[n] = s;
-    row[Np + n] = lse[((int64_t)b * nH + h) * N + n] * LOG2E;
-    if (n == N - 1)
-      for (int k = N; k < Np; ++k) { row[k] = 0.f; row[Np + k] = 0.f; }
-  }
-}
-
-// A fragment whose reduction index follows the C-layout permutation of a 32-wide k step (see attn_fast.hip)
-MTT_DEV u32x4 perm_frag(const unsigned char* tile, int row, int ks, int lg) {
-  const u32x2 lo = *(const u32x2*)(tile + lds_off(row, 4 * ks + (lg >> 1)) + (lg & 1) * 8);
-  const u32x2 hi = *(const u32x2*)(tile + lds_off(row, 4 * ks + 2 + (lg >> 1)) + (lg & 1) * 8);
-  return (u32x4){lo[0], lo[1], hi[0], hi[1]};
-}
-
-// 4-row x 8-column units of a 64-row tile: 128 threads stage one operand row-major (and transposed when TR)
-template <bool TR>
-MTT_DEV void store_units(unsigned char* rowmajor, unsigned char* transposed, const u32x4 (&sh)[4], int kq, int rb) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) *(u32x4*)(rowmajor + lds_off(kq * 4 + i, rb)) = sh[i];
-  if (TR) {
-    u32x2 piece[8];
-    transpose4x8(sh, piece);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) *(u32x2*)(transposed + lds_off(rb * 8 + j, kq >> 1) + (kq & 1) * 8) = piece[j];
-  }
-}
-
-// ---- VER 2 staging (see attn_fast.hip): tiles go HBM -> LDS by LDS-DMA as they sit in memory ([64 rows][8 chunks of 16 B]); the transposed
-// A fragments (K^T, Q^T, dO^T) come from ds_read_b64_tr_b16 on the SAME row-major image, so no transposed copy is staged at all (the dQ
-// kernel stages 16 KiB per tile instead of 24, the dK/dV kernel 16 instead of 32).  One swizzle serves both read kinds: 16-byte chunk c of
-// row r sits at position c ^ x(r), x(r) = ((r >> 1) & 3) << 1 | ((r >> 3) & 1): the 16 rows of a ds_read_b128 fragment read hit 16
+// ---- staging (see attn_fast.hip): tiles go HBM -> LDS by LDS-DMA as they sit in memory ([64 rows][8 chunks of 16 B]); the transposed
+// A fragments (K^T, Q^T, dO^T) come from ds_read_b64_tr_b16 on the SAME row-major image, so no transposed copy is staged at all (both
+// kernels stage 16 KiB per tile).  One swizzle serves both read kinds: 16-byte chunk c of row r sits at position c ^ x(r), x(r) = ((r >> 1) & 3) << 1 | ((r >> 3) & 1): the 16 rows of a ds_read_b128 fragment read hit 16
 // different (row parity, position) pairs, and the 8 rows a 32-lane half of a transpose read touches hit 8 different 32-byte units.
 __device__ __attribute__((aligned(32))) const unsigned g_bwd_zero_page[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 MTT_DEV int bwd_swz(int row) { return (((row >> 1) & 3) << 1) | ((row >> 3) & 1); }
@@ -113,8 +63,7 @@ MTT_DEV void bwd_glds4(const float* src, unsigned char* lds_wave_base) {   // 64
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
 }
-// tile kinds of the VER 2 loops: a compile-time 0 / 1, or -1 = decided at run time (VER 0 / VER 1 and the MTT_ABWD_TILES=0 build)
-using BwdDyn = std::integral_constant<int, -1>;
+// tile kinds (and LDS stage) of the loops: a compile-time 0 / 1
 using BwdNo = std::integral_constant<int, 0>;
 using BwdYes = std::integral_constant<int, 1>;
 template <int OFF>
@@ -134,23 +83,16 @@ MTT_DEV f32x4 bwd_ds_read_f4(unsigned addr) {
 // can be placed above the wait — the asm loads are invisible to the compiler's own wait counting
 #define BWD_WAIT_TR8(a, b)                                                                                                              \
   asm volatile("s_waitcnt lgkmcnt(0)" : BWD_TRW(a[0]), BWD_TRW(a[1]), BWD_TRW(a[2]), BWD_TRW(a[3]), BWD_TRW(b[0]), BWD_TRW(b[1]), BWD_TRW(b[2]), BWD_TRW(b[3]) :: "memory")
-#define BWD_WAIT_TR16(a, b, c, d)                                                                                                       \
-  asm volatile("s_waitcnt lgkmcnt(0)" : BWD_TRW(a[0]), BWD_TRW(a[1]), BWD_TRW(a[2]), BWD_TRW(a[3]), BWD_TRW(b[0]), BWD_TRW(b[1]), BWD_TRW(b[2]), BWD_TRW(b[3]), \
-               BWD_TRW(c[0]), BWD_TRW(c[1]), BWD_TRW(c[2]), BWD_TRW(c[3]), BWD_TRW(d[0]), BWD_TRW(d[1]), BWD_TRW(d[2]), BWD_TRW(d[3]) :: "memory")
 #define BWD_WAIT_TR16_F4(a, b, c, d, e, f)                                                                                              \
   asm volatile("s_waitcnt lgkmcnt(0)" : BWD_TRW(a[0]), BWD_TRW(a[1]), BWD_TRW(a[2]), BWD_TRW(a[3]), BWD_TRW(b[0]), BWD_TRW(b[1]), BWD_TRW(b[2]), BWD_TRW(b[3]), \
                BWD_TRW(c[0]), BWD_TRW(c[1]), BWD_TRW(c[2]), BWD_TRW(c[3]), BWD_TRW(d[0]), BWD_TRW(d[1]), BWD_TRW(d[2]), BWD_TRW(d[3]),                       \
                BWD_TRW(e[0]), BWD_TRW(e[1]), BWD_TRW(f[0]), BWD_TRW(f[1]) :: "memory")
 
 // --------------------------------------------------------------------------------------------------------
-// VER 2 (default): LDS-DMA staging + transpose reads (above).  VER 1 (MTT_ATTN_FAST_V1): register-staged tiles with a transposed copy;
-// VER 0 = the first form, MTT_ATTN_FAST_V0.
-// VER 1 over VER 0: loop unrolled by the two LDS stages (immediate stage offsets), full tiles
-// staged without per-row predicates, MFMA clusters at raised wave priority — the three changes that took 7 % off the forward kernel.
-template <int VER>
+// Both loops are unrolled by the two LDS stages (immediate stage offsets) and run their MFMA clusters at raised wave priority.
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int STAGE = (VER == 2 ? 2 : 3) * KTILE;  // K, K^T, V (VER 2: K, V)
+  constexpr int STAGE = 2 * KTILE;                  // K, V
   const int nqb = (p.N + 127) / 128;                // XCD-aware 1-D grid: one head's blocks share an XCD's L2
   const int wi = xcd_remap(blockIdx.x, gridDim.x);
   const int qb = wi % nqb, bh_ = wi / nqb;
@@ -160,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
   const int li = lane & 15, lg = lane >> 4;
   const int64_t tok0 = (int64_t)b * N;
   const int64_t bh = (int64_t)b * p.nH + h;
-  if (VER == 2 && qb * 128 >= p.T && bwd_patches_dead(p, b)) {
+  if (qb * 128 >= p.T && bwd_patches_dead(p, b)) {
     // a block of dead patch rows (the blocks the forward skipped): dS = 0 for its rows, so dq = 0.  Its stat entries stay unwritten —
     // the dK/dV kernel does not visit these rows — except the zero padding, which keeps its contract.  No barrier has been reached.
 #pragma unroll
@@ -168,9 +110,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
       const int idx = tid + 256 * i, qrow = qb * 128 + (idx >> 3);
       if (qrow < N) *(u32x4*)(p.dqkv + (tok0 + qrow) * 3 * C + h * HD + (idx & 7) * 8) = (u32x4){0u, 0u, 0u, 0u};
     }
-    if (MTT_ABWD_DQSTAT && qb == nqb - 1 && tid < p.Np - N) {
-      p.stat_w[bh * 2 * p.Np + N + tid] = 0.f;
-      p.stat_w[bh * 2 * p.Np + p.Np + N + tid] = 0.f;
+    if (qb == nqb - 1 && tid < p.Np - N) {
+      p.stat[bh * 2 * p.Np + N + tid] = 0.f;
+      p.stat[bh * 2 * p.Np + p.Np + N + tid] = 0.f;
     }
     return;
   }
@@ -191,94 +133,50 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
       load8_raw<false>(p.dout, (tok0 + qrow) * C + h * HD + kh * 32 + lg * 8, ok, r);
       cvt8<false, false>(ok, r, gf[sub][kh], dummy);
     }
-    if constexpr (VER == 2 && MTT_ABWD_DQSTAT) {
-      // D[q] = sum_d dO[q,d] O[q,d] in attn_stat_kernel's order: the 8-element chunk sums, then the pairwise tree over the head's eight
-      // chunks (chunk = 4 kh + lg: partner chunk ^ 1 is lane ^ 16, chunk ^ 2 is lane ^ 32, chunk ^ 4 the other kh register)
-      float c[2];
+    // D[q] = sum_d dO[q,d] O[q,d]: the 8-element chunk sums (dot8_bf16), then the pairwise tree over the head's eight chunks
+    // (chunk = 4 kh + lg: partner chunk ^ 1 is lane ^ 16, chunk ^ 2 is lane ^ 32, chunk ^ 4 the other kh register)
+    float c[2];
 #pragma unroll
-      for (int kh = 0; kh < 2; ++kh) {
-        Raw8<false> r;
-        u32x4 of;
-        load8_raw<false>(p.out, (tok0 + qrow) * C + h * HD + kh * 32 + lg * 8, ok, r);
-        cvt8<false, false>(ok, r, of, dummy);
-        c[kh] = dot8_bf16(of, gf[sub][kh]);
-        c[kh] += __shfl_xor(c[kh], 16, 64);
-        c[kh] += __shfl_xor(c[kh], 32, 64);
-      }
-      Dq[sub] = c[0] + c[1];
-      lse2[sub] = ok ? p.lse[bh * N + qrow] * LOG2E : 0.f;
-      if (ok && lg == 0) {
-        p.stat_w[bh * 2 * p.Np + qrow] = Dq[sub];
-        p.stat_w[bh * 2 * p.Np + p.Np + qrow] = lse2[sub];
-      }
-    } else {
-      Dq[sub] = ok ? p.stat[bh * 2 * p.Np + qrow] : 0.f;
-      lse2[sub] = ok ? p.stat[bh * 2 * p.Np + p.Np + qrow] : 0.f;
+    for (int kh = 0; kh < 2; ++kh) {
+      Raw8<false> r;
+      u32x4 of;
+      load8_raw<false>(p.out, (tok0 + qrow) * C + h * HD + kh * 32 + lg * 8, ok, r);
+      cvt8<false, false>(ok, r, of, dummy);
+      c[kh] = dot8_bf16(of, gf[sub][kh]);
+      c[kh] += __shfl_xor(c[kh], 16, 64);
+      c[kh] += __shfl_xor(c[kh], 32, 64);
+    }
+    Dq[sub] = c[0] + c[1];
+    lse2[sub] = ok ? p.lse[bh * N + qrow] * LOG2E : 0.f;
+    if (ok && lg == 0) {
+      p.stat[bh * 2 * p.Np + qrow] = Dq[sub];
+      p.stat[bh * 2 * p.Np + p.Np + qrow] = lse2[sub];
     }
   }
-  if constexpr (VER == 2 && MTT_ABWD_DQSTAT) {         // the head's last block zeroes the padding [N, Np) of both stat rows
-    if (qb == nqb - 1 && tid < p.Np - N) {
-      p.stat_w[bh * 2 * p.Np + N + tid] = 0.f;
-      p.stat_w[bh * 2 * p.Np + p.Np + N + tid] = 0.f;
-    }
+  if (qb == nqb - 1 && tid < p.Np - N) {               // the head's last block zeroes the padding [N, Np) of both stat rows
+    p.stat[bh * 2 * p.Np + N + tid] = 0.f;
+    p.stat[bh * 2 * p.Np + p.Np + N + tid] = 0.f;
   }
 
-  const bool isK = tid < 128;
-  const int kq = tid & 15, rb = (tid >> 4) & 7;
-  Raw8<false> raw[4];
-  unsigned okm = 0;
-  auto stage_load = [&](int kv0) {
-    if (VER >= 1 && kv0 + 64 <= N) {                  // block-uniform: a full tile needs no per-key selects
-      okm = 0xfu;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        raw[i].r0 = *(const u32x4*)(p.qkv + ((tok0 + kv0 + kq * 4 + i) * 3 * C + (isK ? C : 2 * C) + h * HD + rb * 8));
-      return;
-    }
-    okm = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int key = kv0 + kq * 4 + i;
-      const bool ok = key < N;
-      okm |= (ok ? 1u : 0u) << i;
-      load8_raw<false>(p.qkv, (tok0 + key) * 3 * C + (isK ? C : 2 * C) + h * HD + rb * 8, ok, raw[i]);
-    }
-  };
-  auto stage_store = [&](unsigned char* st) {
-    u32x4 sh[4];
-    if (VER >= 1 && okm == 0xfu) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) sh[i] = raw[i].r0;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) cvt8<false, false>((okm >> i) & 1u, raw[i], sh[i], dummy);
-    }
-    if (isK) store_units<true>(st, st + KTILE, sh, kq, rb);
-    else store_units<false>(st + 2 * KTILE, nullptr, sh, kq, rb);
-  };
-
-  // VER 2: wave w moves key rows [16 w, 16 w + 16) of the K and of the V tile as two 1-KiB pieces each
+  // wave w moves key rows [16 w, 16 w + 16) of the K and of the V tile as two 1-KiB pieces each
   int dma_off[4], dma_row[2];
-  uint64_t zpage = 0;
-  unsigned taddr[4];                                 // K^T transpose-read addresses per d tile (stage, 32-key half, 4-key half: immediates)
-  const unsigned char* faddr[2];                     // row fragment (ds_read_b128) addresses per kh (key tile, stage, K / V: immediates)
-  if (VER == 2) {
-    zpage = (uint64_t)(uintptr_t)g_bwd_zero_page;
-    asm volatile("" : "+s"(zpage));
+  uint64_t zpage = (uint64_t)(uintptr_t)g_bwd_zero_page;
+  asm volatile("" : "+s"(zpage));
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int r = wave * 16 + i * 8 + (lane >> 3), pc = lane & 7;
-      dma_row[i] = r;
-      dma_off[i] = r * 3 * C + C + ((pc ^ bwd_swz(r)) & 7) * 8;
-      dma_off[2 + i] = r * 3 * C + 2 * C + ((pc ^ bwd_swz(r)) & 7) * 8;
-    }
-    const int trow = 4 * lg + (li >> 2);
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-      taddr[dt] = (unsigned)(uintptr_t)smem + (unsigned)(trow * 128 + (((2 * dt + ((li & 3) >> 1)) ^ bwd_swz(trow)) & 7) * 16 + (li & 1) * 8);
-#pragma unroll
-    for (int kh = 0; kh < 2; ++kh) faddr[kh] = smem + li * 128 + (((kh * 4 + lg) ^ bwd_swz(li)) & 7) * 16;
+  for (int i = 0; i < 2; ++i) {
+    const int r = wave * 16 + i * 8 + (lane >> 3), pc = lane & 7;
+    dma_row[i] = r;
+    dma_off[i] = r * 3 * C + C + ((pc ^ bwd_swz(r)) & 7) * 8;
+    dma_off[2 + i] = r * 3 * C + 2 * C + ((pc ^ bwd_swz(r)) & 7) * 8;
   }
+  unsigned taddr[4];                                 // K^T transpose-read addresses per d tile (stage, 32-key half, 4-key half: immediates)
+  const int trow = 4 * lg + (li >> 2);
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+    taddr[dt] = (unsigned)(uintptr_t)smem + (unsigned)(trow * 128 + (((2 * dt + ((li & 3) >> 1)) ^ bwd_swz(trow)) & 7) * 16 + (li & 1) * 8);
+  const unsigned char* faddr[2];                     // row fragment (ds_read_b128) addresses per kh (key tile, stage, K / V: immediates)
+#pragma unroll
+  for (int kh = 0; kh < 2; ++kh) faddr[kh] = smem + li * 128 + (((kh * 4 + lg) ^ bwd_swz(li)) & 7) * 16;
   auto dma_issue = [&](unsigned char* st, int kv0) {
     const bf16_t* base = p.qkv + ((tok0 + kv0) * 3 * C + h * HD);
     unsigned char* dK = st + wave * 2048;
@@ -311,87 +209,55 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
   const bool add_raw = p.drawlog != nullptr && p.T > 0 && qb == 0 && wave == 0 && li < p.T;
 
   const int nkv = (N + 63) / 64;
-  if (VER == 2) {
-    dma_issue(smem, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
-    stage_load(0);
-    stage_store(smem);
-  }
+  dma_issue(smem, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  // RG: the key tile is ragged (1) / full (0); RW: the block's wave 0 adds drawlog (1) / nobody does (0); -1 = found out at run time
+  // RG: the key tile is ragged (1) / full (0); RW: the block's wave 0 adds drawlog (1) / nobody does (0)
   auto tile = [&](auto stage_tag, auto ragged_tag, auto raw_tag, int j) {
-    constexpr int ST = decltype(stage_tag)::value;   // -1: run-time stage (VER 0)
+    constexpr int ST = decltype(stage_tag)::value;
     constexpr int RG = decltype(ragged_tag)::value, RW = decltype(raw_tag)::value;
-    const bool more = RG != 1 && j + 1 < nkv;         // a tile known to be ragged at compile time is the last one
-    if (more) {
-      if (VER == 2) dma_issue(smem + (1 - ST) * STAGE, (j + 1) * 64);
-      else stage_load((j + 1) * 64);
-    }
-    const unsigned char* Kh = smem + (ST < 0 ? (j & 1) : ST) * STAGE;
-    const unsigned char* Kt = Kh + KTILE;
-    const unsigned char* Vh = Kh + 2 * KTILE;
+    const bool more = RG != 1 && j + 1 < nkv;         // a ragged tile is the last one
+    if (more) dma_issue(smem + (1 - ST) * STAGE, (j + 1) * 64);
     const int kv0 = j * 64;
     if (active) {
-      const bool full = RG < 0 ? kv0 + 64 <= N : RG == 0;
+      constexpr bool full = RG == 0;
       const bool do_raw = RW != 0 && add_raw;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {                 // two 32-key halves: keeps the live score registers at 2 x [2][2] tiles
         if (RG != 0 && kv0 + 32 * ks >= N) continue;   // (block-uniform) nothing valid in this half of the last tile
         f32x4 s[2][2], dp[2][2];
-        u32x2 ktl[4], kth[4];                          // VER 2: K^T fragments of this half (transpose reads)
-        if constexpr (VER == 2) {
-          u32x4 kf[2][2], vf[2][2];                    // every LDS read of the half in flight before the first MFMA
+        u32x2 ktl[4], kth[4];                          // K^T fragments of this half (transpose reads)
+        u32x4 kf[2][2], vf[2][2];                      // every LDS read of the half in flight before the first MFMA
 #pragma unroll
-          for (int k2 = 0; k2 < 2; ++k2)
+        for (int k2 = 0; k2 < 2; ++k2)
 #pragma unroll
-            for (int kh = 0; kh < 2; ++kh) {
-              kf[k2][kh] = *(const u32x4*)(faddr[kh] + ST * STAGE + k2 * 2048 + (ks ? 4096 : 0));
-              vf[k2][kh] = *(const u32x4*)(faddr[kh] + ST * STAGE + KTILE + k2 * 2048 + (ks ? 4096 : 0));
-            }
-          if (ks == 0) {
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) { ktl[dt] = bwd_ds_read_tr16<ST * STAGE>(taddr[dt]); kth[dt] = bwd_ds_read_tr16<ST * STAGE + 16 * 128>(taddr[dt]); }
-          } else {
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) { ktl[dt] = bwd_ds_read_tr16<ST * STAGE + 32 * 128>(taddr[dt]); kth[dt] = bwd_ds_read_tr16<ST * STAGE + 48 * 128>(taddr[dt]); }
+          for (int kh = 0; kh < 2; ++kh) {
+            kf[k2][kh] = *(const u32x4*)(faddr[kh] + ST * STAGE + k2 * 2048 + (ks ? 4096 : 0));
+            vf[k2][kh] = *(const u32x4*)(faddr[kh] + ST * STAGE + KTILE + k2 * 2048 + (ks ? 4096 : 0));
           }
-          BWD_WAIT_TR8(ktl, kth);
-          __builtin_amdgcn_s_setprio(1);
+        if (ks == 0) {
 #pragma unroll
-          for (int k2 = 0; k2 < 2; ++k2) {
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub) { s[sub][k2] = (f32x4){0.f, 0.f, 0.f, 0.f}; dp[sub][k2] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-              for (int sub = 0; sub < 2; ++sub) {
-                s[sub][k2] = mfma16(kf[k2][kh], qf[sub][kh], s[sub][k2]);
-                dp[sub][k2] = mfma16(vf[k2][kh], gf[sub][kh], dp[sub][k2]);
-              }
-          }
-          __builtin_amdgcn_s_setprio(0);
+          for (int dt = 0; dt < 4; ++dt) { ktl[dt] = bwd_ds_read_tr16<ST * STAGE>(taddr[dt]); kth[dt] = bwd_ds_read_tr16<ST * STAGE + 16 * 128>(taddr[dt]); }
         } else {
-        if (VER >= 1) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) { ktl[dt] = bwd_ds_read_tr16<ST * STAGE + 32 * 128>(taddr[dt]); kth[dt] = bwd_ds_read_tr16<ST * STAGE + 48 * 128>(taddr[dt]); }
+        }
+        BWD_WAIT_TR8(ktl, kth);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2) {
-          const int kt = 2 * ks + k2;
 #pragma unroll
           for (int sub = 0; sub < 2; ++sub) { s[sub][k2] = (f32x4){0.f, 0.f, 0.f, 0.f}; dp[sub][k2] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
-          for (int kh = 0; kh < 2; ++kh) {
-            const u32x4 kf = *(const u32x4*)(Kh + lds_off(kt * 16 + li, kh * 4 + lg));
-            const u32x4 vf = *(const u32x4*)(Vh + lds_off(kt * 16 + li, kh * 4 + lg));
+          for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub) {
-              s[sub][k2] = mfma16(kf, qf[sub][kh], s[sub][k2]);
-              dp[sub][k2] = mfma16(vf, gf[sub][kh], dp[sub][k2]);
+              s[sub][k2] = mfma16(kf[k2][kh], qf[sub][kh], s[sub][k2]);
+              dp[sub][k2] = mfma16(vf[k2][kh], gf[sub][kh], dp[sub][k2]);
             }
-          }
         }
-        if (VER >= 1) __builtin_amdgcn_s_setprio(0);
-        }
+        __builtin_amdgcn_s_setprio(0);
         // s[sub][k2][r] = S[q = li][key = kv0 + 16 (2ks + k2) + 4 lg + r]
         u32x4 dsb[2];
 #pragma unroll
@@ -424,48 +290,34 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
           dsb[sub] = (u32x4){pack2(ds[0][0], ds[0][1]), pack2(ds[0][2], ds[0][3]), pack2(ds[1][0], ds[1][1]), pack2(ds[1][2], ds[1][3])};
         }
         // dQ^T[d][q] += K^T[d][keys of this half] dS^T
-        if (VER >= 1) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          u32x4 ka;
-          if constexpr (VER == 2) ka = (u32x4){ktl[dt][0], ktl[dt][1], kth[dt][0], kth[dt][1]};
-          else ka = perm_frag(Kt, dt * 16 + li, ks, lg);
+          const u32x4 ka = (u32x4){ktl[dt][0], ktl[dt][1], kth[dt][0], kth[dt][1]};
           dq[0][dt] = mfma16(ka, dsb[0], dq[0][dt]);
           dq[1][dt] = mfma16(ka, dsb[1], dq[1][dt]);
         }
-        if (VER >= 1) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
       }
     }
-    if (more) {
-      if (VER == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else stage_store(smem + (ST < 0 ? ((j + 1) & 1) : (1 - ST)) * STAGE);
-    }
+    if (more) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   };
-  if (VER == 2 && MTT_ABWD_TILES) {
-    // full tiles run the select-free body; the ragged last tile (if any) is peeled.  Blocks whose wave 0 adds drawlog (the prompt rows'
-    // block of each head) run their own copy of the loop, so that every other block's body has no trace of the add
-    const int nfull = N / 64;
-    auto run = [&](auto raw_tag) {
-      for (int j = 0; j < nfull; j += 2) {
-        tile(BwdNo{}, BwdNo{}, raw_tag, j);
-        if (j + 1 < nfull) tile(BwdYes{}, BwdNo{}, raw_tag, j + 1);
-      }
-      if (nfull < nkv) {
-        if (nfull & 1) tile(BwdYes{}, BwdYes{}, raw_tag, nfull);
-        else tile(BwdNo{}, BwdYes{}, raw_tag, nfull);
-      }
-    };
-    if (p.drawlog != nullptr && p.T > 0 && qb == 0) run(BwdYes{});
-    else run(BwdNo{});
-  } else if (VER >= 1) {
-    for (int j = 0; j < nkv; j += 2) {
-      tile(BwdNo{}, BwdDyn{}, BwdDyn{}, j);
-      if (j + 1 < nkv) tile(BwdYes{}, BwdDyn{}, BwdDyn{}, j + 1);
+  // full tiles run the select-free body; the ragged last tile (if any) is peeled.  Blocks whose wave 0 adds drawlog (the prompt rows'
+  // block of each head) run their own copy of the loop, so that every other block's body has no trace of the add
+  const int nfull = N / 64;
+  auto run = [&](auto raw_tag) {
+    for (int j = 0; j < nfull; j += 2) {
+      tile(BwdNo{}, BwdNo{}, raw_tag, j);
+      if (j + 1 < nfull) tile(BwdYes{}, BwdNo{}, raw_tag, j + 1);
     }
-  } else {
-    for (int j = 0; j < nkv; ++j) tile(BwdDyn{}, BwdDyn{}, BwdDyn{}, j);
-  }
+    if (nfull < nkv) {
+      if (nfull & 1) tile(BwdYes{}, BwdYes{}, raw_tag, nfull);
+      else tile(BwdNo{}, BwdYes{}, raw_tag, nfull);
+    }
+  };
+  if (p.drawlog != nullptr && p.T > 0 && qb == 0) run(BwdYes{});
+  else run(BwdNo{});
   // dq[sub][dt][r] = dQ[q = li][d = 16 dt + 4 lg + r] / scale
 #pragma unroll
   for (int sub = 0; sub < 2; ++sub) {
@@ -479,10 +331,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const BwdP p) {
 }
 
 // --------------------------------------------------------------------------------------------------------
-template <int VER>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int STAGE = (VER == 2 ? 2 : 4) * KTILE;  // Q, Q^T, dO, dO^T (VER 2: Q, dO)
+  constexpr int STAGE = 2 * KTILE;                  // Q, dO
   const int nkb = (p.N + 127) / 128;
   const int wi = xcd_remap(blockIdx.x, gridDim.x);
   const int kb = wi % nkb, bh_ = wi / nkb;
@@ -510,73 +361,33 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
     }
   }
 
-  const bool isQ = tid < 128;
-  const int kq = tid & 15, rb = (tid >> 4) & 7;
-  Raw8<false> raw[4];
-  unsigned okm = 0;
-  auto stage_load = [&](int q0) {
-    if (VER >= 1 && q0 + 64 <= N) {                   // block-uniform: a full tile needs no per-row selects
-      okm = 0xfu;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t row = tok0 + q0 + kq * 4 + i;
-        raw[i].r0 = isQ ? *(const u32x4*)(p.qkv + (row * 3 * C + h * HD + rb * 8)) : *(const u32x4*)(p.dout + (row * C + h * HD + rb * 8));
-      }
-      return;
-    }
-    okm = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = q0 + kq * 4 + i;
-      const bool ok = row < N;
-      okm |= (ok ? 1u : 0u) << i;
-      if (isQ) load8_raw<false>(p.qkv, (tok0 + row) * 3 * C + h * HD + rb * 8, ok, raw[i]);
-      else load8_raw<false>(p.dout, (tok0 + row) * C + h * HD + rb * 8, ok, raw[i]);
-    }
-  };
-  auto stage_store = [&](unsigned char* st) {
-    u32x4 sh[4];
-    if (VER >= 1 && okm == 0xfu) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) sh[i] = raw[i].r0;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) cvt8<false, false>((okm >> i) & 1u, raw[i], sh[i], dummy);
-    }
-    unsigned char* base = isQ ? st : st + 2 * KTILE;
-    store_units<true>(base, base + KTILE, sh, kq, rb);
-  };
-
-  // VER 2: wave w moves query rows [16 w, 16 w + 16) of the Q and of the dO tile as two 1-KiB pieces each
+  // wave w moves query rows [16 w, 16 w + 16) of the Q and of the dO tile as two 1-KiB pieces each
   int dma_off[4], dma_row[2];
-  uint64_t zpage = 0;
-  unsigned taddr[4];                                 // Q^T / dO^T transpose-read addresses per d tile
-  const unsigned char* faddr[2];                     // row fragment addresses per kh
-  if (VER == 2) {
-    zpage = (uint64_t)(uintptr_t)g_bwd_zero_page;
-    asm volatile("" : "+s"(zpage));
+  uint64_t zpage = (uint64_t)(uintptr_t)g_bwd_zero_page;
+  asm volatile("" : "+s"(zpage));
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int r = wave * 16 + i * 8 + (lane >> 3), pc = lane & 7;
-      dma_row[i] = r;
-      dma_off[i] = r * 3 * C + ((pc ^ bwd_swz(r)) & 7) * 8;
-      dma_off[2 + i] = r * C + ((pc ^ bwd_swz(r)) & 7) * 8;
-    }
-    const int trow = 4 * lg + (li >> 2);
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-      taddr[dt] = (unsigned)(uintptr_t)smem + (unsigned)(trow * 128 + (((2 * dt + ((li & 3) >> 1)) ^ bwd_swz(trow)) & 7) * 16 + (li & 1) * 8);
-#pragma unroll
-    for (int kh = 0; kh < 2; ++kh) faddr[kh] = smem + li * 128 + (((kh * 4 + lg) ^ bwd_swz(li)) & 7) * 16;
+  for (int i = 0; i < 2; ++i) {
+    const int r = wave * 16 + i * 8 + (lane >> 3), pc = lane & 7;
+    dma_row[i] = r;
+    dma_off[i] = r * 3 * C + ((pc ^ bwd_swz(r)) & 7) * 8;
+    dma_off[2 + i] = r * C + ((pc ^ bwd_swz(r)) & 7) * 8;
   }
+  unsigned taddr[4];                                 // Q^T / dO^T transpose-read addresses per d tile
+  const int trow = 4 * lg + (li >> 2);
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+    taddr[dt] = (unsigned)(uintptr_t)smem + (unsigned)(trow * 128 + (((2 * dt + ((li & 3) >> 1)) ^ bwd_swz(trow)) & 7) * 16 + (li & 1) * 8);
+  const unsigned char* faddr[2];                     // row fragment addresses per kh
+#pragma unroll
+  for (int kh = 0; kh < 2; ++kh) faddr[kh] = smem + li * 128 + (((kh * 4 + lg) ^ bwd_swz(li)) & 7) * 16;
   const float* Drow = p.stat + bh * 2 * p.Np;
   const float* Lrow = Drow + p.Np;
-  // MTT_ABWD_STATDMA: behind the two stages, per stage 64 D values then 64 lse*log2(e) values of the tile's query rows (wave 0 moves the
-  // D piece, wave 1 the other); a lane reads the four rows 4 lg .. 4 lg + 3 of a 16-row sub-tile as one 16-byte LDS read
+  // the per-row statistics sit behind the two stages, per stage 64 D values then 64 lse*log2(e) values of the tile's query rows (wave 0 moves
+  // the D piece, wave 1 the other); a lane reads the four rows 4 lg .. 4 lg + 3 of a 16-row sub-tile as one 16-byte LDS read
   constexpr int STAT_LDS = 2 * STAGE, STAT_STAGE = 2 * 64 * 4;
   const unsigned saddr = (unsigned)(uintptr_t)smem + (unsigned)(lg * 16);   // read by asm like the transposed fragments: see BWD_WAIT_TR8
   auto dma_issue = [&](unsigned char* st, unsigned char* sst, int q0) {
-    if (MTT_ABWD_STATDMA && __builtin_amdgcn_readfirstlane(wave) < 2) {
+    if (__builtin_amdgcn_readfirstlane(wave) < 2) {
       const float* src = (wave ? Lrow : Drow) + q0 + lane;
       if (q0 + 64 > p.Np) src = q0 + lane < p.Np ? src : (const float*)(uintptr_t)zpage;   // rows past the zero padding of stat
       bwd_glds4(src, sst + wave * 256);
@@ -612,131 +423,86 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
   const float sc2 = p.scale * LOG2E, inv_scale = 1.0f / p.scale;
 
   const int nq = (N + 63) / 64;
-  // DropPath skip (VER 2): with the image's patch rows dead, the query tiles past the prompt rows' (a suffix of the loop) carry dO = 0 and add
+  // DropPath skip: with the image's patch rows dead, the query tiles past the prompt rows' (a suffix of the loop) carry dO = 0 and add
   // nothing to dK / dV: only the trip count shrinks, to nlive tiles; the KIND of a tile still follows from the true N.  T == 0: no tile at all.
   int nlive = nq;
-  if (VER == 2 && bwd_patches_dead(p, b)) { const int np = (p.T + 63) / 64; nlive = np < nq ? np : nq; }
-  if (VER == 2) {
-    if (nlive > 0) dma_issue(smem, smem + STAT_LDS, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
-    stage_load(0);
-    stage_store(smem);
-  }
+  if (bwd_patches_dead(p, b)) { const int np = (p.T + 63) / 64; nlive = np < nq ? np : nq; }
+  if (nlive > 0) dma_issue(smem, smem + STAT_LDS, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  // RG: the query tile is ragged (1) / full (0); FT: it is the first one, whose prompt rows take the drawlog add (1) / it is not (0);
-  // -1 = found out at run time
+  // RG: the query tile is ragged (1) / full (0); FT: it is the first one, whose prompt rows take the drawlog add (1) / it is not (0)
   auto tile = [&](auto stage_tag, auto ragged_tag, auto first_tag, int j) {
     constexpr int ST = decltype(stage_tag)::value;
     constexpr int RG = decltype(ragged_tag)::value, FT = decltype(first_tag)::value;
-    const bool more = RG != 1 && j + 1 < nlive;       // a tile known to be ragged at compile time is the last one
-    if (more) {
-      if (VER == 2) dma_issue(smem + (1 - ST) * STAGE, smem + STAT_LDS + (1 - ST) * STAT_STAGE, (j + 1) * 64);
-      else stage_load((j + 1) * 64);
-    }
-    const unsigned char* Qh = smem + (ST < 0 ? (j & 1) : ST) * STAGE;
-    const unsigned char* Qt = Qh + KTILE;
-    const unsigned char* Gh = Qh + 2 * KTILE;
-    const unsigned char* Gt = Qh + 3 * KTILE;
+    const bool more = RG != 1 && j + 1 < nlive;       // a ragged tile is the last one
+    if (more) dma_issue(smem + (1 - ST) * STAGE, smem + STAT_LDS + (1 - ST) * STAT_STAGE, (j + 1) * 64);
     const int q0 = j * 64;
     if (active) {
-      const bool full = RG < 0 ? q0 + 64 <= N : RG == 0;
-      const bool add_raw = FT != 0 && p.drawlog != nullptr && (FT > 0 || j == 0) && p.T > 0;
+      constexpr bool full = RG == 0;
+      const bool add_raw = FT != 0 && p.drawlog != nullptr && p.T > 0;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {                 // two 32-query halves
         if (RG != 0 && q0 + 32 * ks >= N) continue;    // (block-uniform) nothing valid in this half of the last tile
         f32x4 s[2][2], dp[2][2];                       // [q sub of the half][key tile]
         f32x4 D4[2], L4[2];
-        u32x2 qtl[4], qth[4], gtl[4], gth[4];          // VER 2: Q^T / dO^T fragments of this half (transpose reads)
-        if constexpr (VER == 2) {
-          // a peeled ragged tile (runs once per workgroup) carries row masks on top of everything else: its transposed fragments and stat
-          // values are read after the S / dP MFMAs, when the row fragments are dead.  Every other tile has all LDS reads of the half in
-          // flight before the first MFMA
-          constexpr bool LATE = RG == 1;
-          u32x4 qa[2][2], ga[2][2];
-          auto read_stat = [&]() {
-#pragma unroll
-            for (int q2 = 0; q2 < 2; ++q2) {
-              D4[q2] = bwd_ds_read_f4<STAT_LDS + ST * STAT_STAGE>(saddr + (ks ? 128 : 0) + q2 * 64);
-              L4[q2] = bwd_ds_read_f4<STAT_LDS + ST * STAT_STAGE + 256>(saddr + (ks ? 128 : 0) + q2 * 64);
-            }
-          };
-          auto read_tr = [&]() {
-            if (ks == 0) {
-#pragma unroll
-              for (int dt = 0; dt < 4; ++dt) {
-                qtl[dt] = bwd_ds_read_tr16<ST * STAGE>(taddr[dt]); qth[dt] = bwd_ds_read_tr16<ST * STAGE + 16 * 128>(taddr[dt]);
-                gtl[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE>(taddr[dt]); gth[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE + 16 * 128>(taddr[dt]);
-              }
-            } else {
-#pragma unroll
-              for (int dt = 0; dt < 4; ++dt) {
-                qtl[dt] = bwd_ds_read_tr16<ST * STAGE + 32 * 128>(taddr[dt]); qth[dt] = bwd_ds_read_tr16<ST * STAGE + 48 * 128>(taddr[dt]);
-                gtl[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE + 32 * 128>(taddr[dt]); gth[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE + 48 * 128>(taddr[dt]);
-              }
-            }
-          };
-          auto wait_reads = [&]() {
-            if constexpr (MTT_ABWD_STATDMA) BWD_WAIT_TR16_F4(qtl, qth, gtl, gth, D4, L4);
-            else BWD_WAIT_TR16(qtl, qth, gtl, gth);
-          };
-          if constexpr (MTT_ABWD_STATDMA && !LATE) read_stat();
+        u32x2 qtl[4], qth[4], gtl[4], gth[4];          // Q^T / dO^T fragments of this half (transpose reads)
+        // a peeled ragged tile (runs once per workgroup) carries row masks on top of everything else: its transposed fragments and stat
+        // values are read after the S / dP MFMAs, when the row fragments are dead.  Every other tile has all LDS reads of the half in
+        // flight before the first MFMA
+        constexpr bool LATE = RG == 1;
+        u32x4 qa[2][2], ga[2][2];
+        auto read_stat = [&]() {
 #pragma unroll
           for (int q2 = 0; q2 < 2; ++q2) {
-            if constexpr (!MTT_ABWD_STATDMA) {
-              const int qr = q0 + (2 * ks + q2) * 16 + lg * 4;
-              D4[q2] = qr < p.Np ? *(const f32x4*)(Drow + qr) : (f32x4){0.f, 0.f, 0.f, 0.f};
-              L4[q2] = qr < p.Np ? *(const f32x4*)(Lrow + qr) : (f32x4){0.f, 0.f, 0.f, 0.f};
+            D4[q2] = bwd_ds_read_f4<STAT_LDS + ST * STAT_STAGE>(saddr + (ks ? 128 : 0) + q2 * 64);
+            L4[q2] = bwd_ds_read_f4<STAT_LDS + ST * STAT_STAGE + 256>(saddr + (ks ? 128 : 0) + q2 * 64);
+          }
+        };
+        auto read_tr = [&]() {
+          if (ks == 0) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+              qtl[dt] = bwd_ds_read_tr16<ST * STAGE>(taddr[dt]); qth[dt] = bwd_ds_read_tr16<ST * STAGE + 16 * 128>(taddr[dt]);
+              gtl[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE>(taddr[dt]); gth[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE + 16 * 128>(taddr[dt]);
             }
+          } else {
 #pragma unroll
-            for (int kh = 0; kh < 2; ++kh) {
-              qa[q2][kh] = *(const u32x4*)(faddr[kh] + ST * STAGE + q2 * 2048 + (ks ? 4096 : 0));
-              ga[q2][kh] = *(const u32x4*)(faddr[kh] + ST * STAGE + KTILE + q2 * 2048 + (ks ? 4096 : 0));
+            for (int dt = 0; dt < 4; ++dt) {
+              qtl[dt] = bwd_ds_read_tr16<ST * STAGE + 32 * 128>(taddr[dt]); qth[dt] = bwd_ds_read_tr16<ST * STAGE + 48 * 128>(taddr[dt]);
+              gtl[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE + 32 * 128>(taddr[dt]); gth[dt] = bwd_ds_read_tr16<ST * STAGE + KTILE + 48 * 128>(taddr[dt]);
             }
           }
-          if constexpr (!LATE) { read_tr(); wait_reads(); }
-          __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-          for (int q2 = 0; q2 < 2; ++q2) {
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) { s[q2][kt] = (f32x4){0.f, 0.f, 0.f, 0.f}; dp[q2][kt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-              for (int kt = 0; kt < 2; ++kt) {
-                s[q2][kt] = mfma16(qa[q2][kh], kf[kt][kh], s[q2][kt]);
-                dp[q2][kt] = mfma16(ga[q2][kh], vf[kt][kh], dp[q2][kt]);
-              }
-          }
-          __builtin_amdgcn_s_setprio(0);
-          if constexpr (LATE) {
-            if constexpr (MTT_ABWD_STATDMA) read_stat();
-            read_tr();
-            wait_reads();
-          }
-        } else {
-        if (VER >= 1) __builtin_amdgcn_s_setprio(1);
+        };
+        auto wait_reads = [&]() { BWD_WAIT_TR16_F4(qtl, qth, gtl, gth, D4, L4); };
+        if constexpr (!LATE) read_stat();
 #pragma unroll
         for (int q2 = 0; q2 < 2; ++q2) {
-          const int qs = 2 * ks + q2;
-          const int qr = q0 + qs * 16 + lg * 4;        // stat rows are padded to a multiple of 4 (zeros)
-          D4[q2] = qr < p.Np ? *(const f32x4*)(Drow + qr) : (f32x4){0.f, 0.f, 0.f, 0.f};
-          L4[q2] = qr < p.Np ? *(const f32x4*)(Lrow + qr) : (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int kh = 0; kh < 2; ++kh) {
+            qa[q2][kh] = *(const u32x4*)(faddr[kh] + ST * STAGE + q2 * 2048 + (ks ? 4096 : 0));
+            ga[q2][kh] = *(const u32x4*)(faddr[kh] + ST * STAGE + KTILE + q2 * 2048 + (ks ? 4096 : 0));
+          }
+        }
+        if constexpr (!LATE) { read_tr(); wait_reads(); }
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int q2 = 0; q2 < 2; ++q2) {
 #pragma unroll
           for (int kt = 0; kt < 2; ++kt) { s[q2][kt] = (f32x4){0.f, 0.f, 0.f, 0.f}; dp[q2][kt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
-          for (int kh = 0; kh < 2; ++kh) {
-            const u32x4 qa = *(const u32x4*)(Qh + lds_off(qs * 16 + li, kh * 4 + lg));
-            const u32x4 ga = *(const u32x4*)(Gh + lds_off(qs * 16 + li, kh * 4 + lg));
+          for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt) {
-              s[q2][kt] = mfma16(qa, kf[kt][kh], s[q2][kt]);
-              dp[q2][kt] = mfma16(ga, vf[kt][kh], dp[q2][kt]);
+              s[q2][kt] = mfma16(qa[q2][kh], kf[kt][kh], s[q2][kt]);
+              dp[q2][kt] = mfma16(ga[q2][kh], vf[kt][kh], dp[q2][kt]);
             }
-          }
         }
-        if (VER >= 1) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
+        if constexpr (LATE) {
+          read_stat();
+          read_tr();
+          wait_reads();
         }
         // s[q2][kt][r] = S[q = q0 + 16 (2ks + q2) + 4 lg + r][key = key0 + 16 kt + li]
         u32x4 pb[2], dsb[2];
@@ -766,55 +532,37 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const BwdP p) {
           dsb[kt] = (u32x4){pack2(ds[0][0], ds[0][1]), pack2(ds[0][2], ds[0][3]), pack2(ds[1][0], ds[1][1]), pack2(ds[1][2], ds[1][3])};
         }
         // dV^T[d][key] += dO^T[d][q half] P ;  dK^T[d][key] += Q^T[d][q half] dS
-        if (VER >= 1) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          u32x4 ga, qa;
-          if constexpr (VER == 2) {
-            ga = (u32x4){gtl[dt][0], gtl[dt][1], gth[dt][0], gth[dt][1]};
-            qa = (u32x4){qtl[dt][0], qtl[dt][1], qth[dt][0], qth[dt][1]};
-          } else {
-            ga = perm_frag(Gt, dt * 16 + li, ks, lg);
-            qa = perm_frag(Qt, dt * 16 + li, ks, lg);
-          }
+          const u32x4 ga = (u32x4){gtl[dt][0], gtl[dt][1], gth[dt][0], gth[dt][1]};
+          const u32x4 qa = (u32x4){qtl[dt][0], qtl[dt][1], qth[dt][0], qth[dt][1]};
 #pragma unroll
           for (int kt = 0; kt < 2; ++kt) {
             dv[kt][dt] = mfma16(ga, pb[kt], dv[kt][dt]);
             dk[kt][dt] = mfma16(qa, dsb[kt], dk[kt][dt]);
           }
         }
-        if (VER >= 1) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
       }
     }
-    if (more) {
-      if (VER == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else stage_store(smem + (ST < 0 ? ((j + 1) & 1) : (1 - ST)) * STAGE);
-    }
+    if (more) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   };
-  if (VER == 2 && MTT_ABWD_TILES) {
-    // the first tile (drawlog add on its prompt rows) and the ragged last tile are peeled; the tiles between run the body without selects
-    const int nfull = N / 64;
-    const int nlf = nfull < nlive ? nfull : nlive;     // live full tiles
-    if (nlive >= 1) {
-      if (nfull >= 1) tile(BwdNo{}, BwdNo{}, BwdYes{}, 0);
-      else tile(BwdNo{}, BwdYes{}, BwdYes{}, 0);
-    }
-    for (int j = 1; j < nlf; j += 2) {
-      tile(BwdYes{}, BwdNo{}, BwdNo{}, j);
-      if (j + 1 < nlf) tile(BwdNo{}, BwdNo{}, BwdNo{}, j + 1);
-    }
-    if (nfull >= 1 && nfull < nq && nlive == nq) {
-      if (nfull & 1) tile(BwdYes{}, BwdYes{}, BwdNo{}, nfull);
-      else tile(BwdNo{}, BwdYes{}, BwdNo{}, nfull);
-    }
-  } else if (VER >= 1) {
-    for (int j = 0; j < nq; j += 2) {
-      tile(BwdNo{}, BwdDyn{}, BwdDyn{}, j);
-      if (j + 1 < nq) tile(BwdYes{}, BwdDyn{}, BwdDyn{}, j + 1);
-    }
-  } else {
-    for (int j = 0; j < nq; ++j) tile(BwdDyn{}, BwdDyn{}, BwdDyn{}, j);
+  // the first tile (drawlog add on its prompt rows) and the ragged last tile are peeled; the tiles between run the body without selects
+  const int nfull = N / 64;
+  const int nlf = nfull < nlive ? nfull : nlive;       // live full tiles
+  if (nlive >= 1) {
+    if (nfull >= 1) tile(BwdNo{}, BwdNo{}, BwdYes{}, 0);
+    else tile(BwdNo{}, BwdYes{}, BwdYes{}, 0);
+  }
+  for (int j = 1; j < nlf; j += 2) {
+    tile(BwdYes{}, BwdNo{}, BwdNo{}, j);
+    if (j + 1 < nlf) tile(BwdNo{}, BwdNo{}, BwdNo{}, j + 1);
+  }
+  if (nfull >= 1 && nfull < nq && nlive == nq) {
+    if (nfull & 1) tile(BwdYes{}, BwdYes{}, BwdNo{}, nfull);
+    else tile(BwdNo{}, BwdYes{}, BwdNo{}, nfull);
   }
   // dk[kt][dt][r] = dK[key = key0 + 16 kt + li][d = 16 dt + 4 lg + r] / scale
   int tid_e = tid;                                     // the store addresses are rebuilt from the thread index here, so that no row index or
@@ -841,34 +589,14 @@ extern "C" int mtt_attn_bwd(const mtt_attn_desc* d, const void* dout, const floa
   if (d->dtype != MTT_BF16 || d->prec != MTT_PREC_BF16) return MTT_E_UNSUPPORTED;
   if (((uintptr_t)d->qkv | (uintptr_t)dout | (uintptr_t)d->out | (uintptr_t)stat | (uintptr_t)dqkv) & 15) return MTT_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
-  constexpr int smem_dq = 2 * 3 * KTILE, smem_dkv = 2 * 4 * KTILE, smem_dma = 2 * 2 * KTILE;
-  constexpr int smem_dma_dkv = smem_dma + (MTT_ABWD_STATDMA ? 2 * 2 * 64 * 4 : 0);   // + D and lse*log2(e) of each stage's 64 query rows
-  static std::atomic<unsigned long long> done_dq0{0}, done_dkv0{0}, done_dq1{0}, done_dkv1{0};
-  const int ver = d->variant == MTT_ATTN_FAST_V0 ? 0 : d->variant == MTT_ATTN_FAST_V1 ? 1 : 2;
-  if (ver == 0) {
-    if (int e = mtt_ensure_dyn_lds((const void*)attn_bwd_dq_kernel<0>, smem_dq, done_dq0)) return e;
-    if (int e = mtt_ensure_dyn_lds((const void*)attn_bwd_dkv_kernel<0>, smem_dkv, done_dkv0)) return e;
-  } else if (ver == 1) {
-    if (int e = mtt_ensure_dyn_lds((const void*)attn_bwd_dq_kernel<1>, smem_dq, done_dq1)) return e;
-    if (int e = mtt_ensure_dyn_lds((const void*)attn_bwd_dkv_kernel<1>, smem_dkv, done_dkv1)) return e;
-  }                                                  // VER 2 stays within the default 64 KiB of dynamic LDS
+  // two stages of two tiles; the dK/dV kernel adds D and lse*log2(e) of each stage's 64 query rows.  Both stay within the default 64 KiB
+  // of dynamic LDS
+  constexpr int smem_dq = 2 * 2 * KTILE, smem_dkv = smem_dq + 2 * 2 * 64 * 4;
   const int Np = (d->N + 3) & ~3;
-  const int64_t chunks = (int64_t)d->B * d->N * d->nH * 8;
-  if (ver != 2 || !MTT_ABWD_DQSTAT)                    // the VER 2 dQ kernel writes stat itself, ahead of the dK/dV launch on the same stream
-    hipLaunchKernelGGL(attn_stat_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, (const bf16_t*)d->out, (const bf16_t*)dout,
-                       d->lse, stat, d->B, d->N, d->nH, Np);
   BwdP p{(const bf16_t*)d->qkv, (const bf16_t*)dout, stat, d->T > 0 ? drawlog : nullptr, (bf16_t*)dqkv, d->B, d->N, d->nH, d->T, Np, d->scale,
-         (const bf16_t*)d->out, d->lse, stat, d->skip_scale};
+         (const bf16_t*)d->out, d->lse, d->skip_scale};
   dim3 grid((unsigned)(((d->N + 127) / 128) * d->nH * d->B));
-  if (ver == 0) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<0>, grid, dim3(256), smem_dq, s, p);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<0>, grid, dim3(256), smem_dkv, s, p);
-  } else if (ver == 1) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<1>, grid, dim3(256), smem_dq, s, p);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<1>, grid, dim3(256), smem_dkv, s, p);
-  } else {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<2>, grid, dim3(256), smem_dma, s, p);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<2>, grid, dim3(256), smem_dma_dkv, s, p);
-  }
+  hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, dim3(256), smem_dq, s, p);    // writes stat, ahead of the dK/dV launch on the same stream
+  hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid, dim3(256), smem_dkv, s, p);
   return (int)hipGetLastError();
 }

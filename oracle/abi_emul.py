@@ -266,7 +266,7 @@ def attn_bwd(**kw):
     raw = q @ k.transpose(-1, -2)
     P = torch.softmax(raw * kw["scale"], dim=-1)
     dP = g @ v.transpose(-1, -2)
-    # D = rowsum(dO * O) over the STORED (bf16) forward output, as attn_stat_kernel forms it (= rowsum(dP * P) up to that rounding)
+    # D = rowsum(dO * O) over the STORED (bf16) forward output, as attn_bwd_dq_kernel forms it (= rowsum(dP * P) up to that rounding)
     O = _rd(kw["out"], torch.arange(B * N * C)).view(B, N, nH, 64).transpose(1, 2)
     D = (g * O).sum(-1, keepdim=True)
     # the kernels (attn_bwd_dq / dkv): P and dS / scale are bf16 MFMA operands of dV = P^T dO, dQ = dS K, dK = dS^T Q
