@@ -811,6 +811,57 @@ size_t mtt_eval_ws_floats(const mtt_eval_desc* d);
 int mtt_eval_map(const mtt_eval_desc* d, void* stream);
 int mtt_eval_accum(const mtt_eval_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Training-batch augmentation on the device (additive exports, ABI 17 unchanged): what the reference composes per sample in numpy and
+ * OpenCV in get_transformations (TaskPrompter/utils/common_config.py:96-124) from data/transforms.py -- RandomScaling, RandomCrop,
+ * RandomHorizontalFlip, PhotoMetricDistortion, Normalize, PadImage, AddIgnoreRegions, ToTensor -- as ONE gather per output pixel.
+ * The random draws are made on the host and live in a table, int32 [B, MTT_AUG_COLS] (floats as their bit patterns), present twice: a
+ * host copy the entry points validate before they launch, and the device copy the kernels read.  A ragged batch is one packed buffer per
+ * key (HWC samples back to back); off / off_host hold each sample's first ELEMENT, int64 [B].
+ *
+ * Host check (MTT_E_BADARG, nothing launched): 1 <= H, W, SH, SW <= 32768; off >= 0 and off + H*W*C <= src_numel; RESIZED, FLIP and
+ * the switches in {0, 1}; SH == H and SW == W unless RESIZED; NTEST in {0, 10}; CHOSEN in [0, 10]; every candidate offset in
+ * [0, max(S - crop, 0)]; HDELTA in [-18, 17].  In the kernels every table value is clamped to those ranges again and every source index
+ * to [0, src_numel - 1]: no content of the device table makes them read outside the packed buffer; writes depend on B, h, w alone.
+ *
+ * Output pixel (y, x) of the h x w result maps back through pad (the crop of Hc x Wc = min(S, crop) sits at (h - Hc) / 2, (w - Wc) / 2),
+ * flip (x -> Wc - 1 - x), crop (candidate CHOSEN) and scale.  One thread per pixel, or per 4 consecutive pixels with 16-byte stores when
+ * w % 4 == 0.  No floating-point atomics, no contraction into FMAs: bitwise reproducible.
+ *
+ * mtt_aug_select  src = the packed semseg maps (fp32, C = 1, labels integral in [0, 255]).  For rows with NTEST = 10 (CHOSEN = 10 on
+ *   entry) candidates 0..9 are histogrammed over the nearest-resampled map (LDS integer histograms); a candidate passes when more than
+ *   one label other than 255 occurs and max / sum < cat_max_ratio in fp64; CHOSEN becomes the first that passes (integer atomic min).
+ * mtt_aug_image   src uint8 or fp32 HWC (C = 3), values in [0, 255].  RESIZED: bilinear, fx = (float)((dx + 0.5) * (src / dst) - 0.5)
+ *   with the product in fp64, taps clamped at both borders, horizontal a0*s0 + a1*s1 then vertical.  photometric: truncation to 8 bits,
+ *   brightness, contrast before (FMODE) or after saturation and hue; each `convert` is clip(v * alpha + beta, 0, 255) truncated;
+ *   saturation and hue each take an RGB -> HSV -> RGB round trip (H in 0..179; integer forward conversion with the 12-bit reciprocal
+ *   tables, float sector inverse, round to nearest even).  Then (v / 255 - mean) / std with IEEE divisions; pad = 0.  out fp32 [B,3,h,w].
+ * mtt_aug_labels  src fp32 HWC, C = 1 (3 for MTT_AUG_NORMALS).  Nearest: sx = min(dx * src / dst, src - 1) in integers.  MTT_AUG_DEPTH:
+ *   divided by SCALE when RESIZED; 0 -> -1 when depth_ignore.  MTT_AUG_NORMALS: x negated under FLIP; a zero vector -> 255 on the three
+ *   channels.  Pad = fill, BEFORE those two rules (as PadImage precedes AddIgnoreRegions).  MTT_AUG_HUMAN_PARTS: flags int32 [B] records
+ *   per image whether a label other than 0 / 255 occurs (integer atomic); a second launch fills the images without one with 255.
+ *   out fp32 [B, C, h, w]. */
+#define MTT_AUG_CANDS 11
+#define MTT_AUG_COLS 40
+enum { MTT_AUG_H = 0, MTT_AUG_W = 1, MTT_AUG_SH = 2, MTT_AUG_SW = 3, MTT_AUG_RESIZED = 4, MTT_AUG_FLIP = 5, MTT_AUG_NTEST = 6, MTT_AUG_CHOSEN = 7,
+       MTT_AUG_CAND_Y = 8, MTT_AUG_CAND_X = 19,
+       MTT_AUG_BRIGHT = 30, MTT_AUG_BETA = 31, MTT_AUG_FMODE = 32, MTT_AUG_CONTRAST = 33, MTT_AUG_CALPHA = 34, MTT_AUG_SAT = 35, MTT_AUG_SALPHA = 36,
+       MTT_AUG_HUE = 37, MTT_AUG_HDELTA = 38, MTT_AUG_SCALE = 39 };
+enum { MTT_AUG_PLAIN = 0, MTT_AUG_DEPTH = 1, MTT_AUG_NORMALS = 2, MTT_AUG_HUMAN_PARTS = 3 };
+typedef struct {
+  const void* src; const int64_t* off; const int64_t* off_host;
+  int32_t* table; const int32_t* table_host;
+  float* out; int32_t* flags;
+  int64_t src_numel;
+  double cat_max_ratio;            /* mtt_aug_select */
+  int32_t B, h, w, C, src_u8, kind, photometric, depth_ignore;
+  float fill, mean[3], std[3];
+} mtt_aug_desc;
+size_t mtt_aug_desc_size(void);
+int mtt_aug_select(const mtt_aug_desc* d, void* stream);
+int mtt_aug_image(const mtt_aug_desc* d, void* stream);
+int mtt_aug_labels(const mtt_aug_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

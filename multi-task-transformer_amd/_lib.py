@@ -246,6 +246,13 @@ class EvalDesc(C.Structure):
                 ("ignore", f32), ("pos_weight", f32), ("min_depth", f32), ("max_depth", f32)]
 
 
+class AugDesc(C.Structure):
+    _fields_ = [("src", ptr), ("off", ptr), ("off_host", ptr), ("table", ptr), ("table_host", ptr), ("out", ptr), ("flags", ptr),
+                ("src_numel", i64), ("cat_max_ratio", C.c_double),
+                ("B", i32), ("h", i32), ("w", i32), ("C", i32), ("src_u8", i32), ("kind", i32), ("photometric", i32), ("depth_ignore", i32),
+                ("fill", f32), ("mean", f32 * 3), ("std", f32 * 3)]
+
+
 # entry point -> (descriptor struct, size index in mtt_desc_size) ; None = positional-argument entry
 DESCS = {
     "loss_fwd": LossDesc,
@@ -316,11 +323,21 @@ EVAL = {"eval_map": EvalDesc, "eval_accum": EvalDesc}
 EVAL_CONFUSION, EVAL_SAL, EVAL_DEPTH, EVAL_NORMALS, EVAL_EDGE = 0, 1, 2, 3, 4     # MTT_EVAL_* of include/mtt_hip.h
 EVAL_FROM_LOGITS, EVAL_FROM_MAP = 0, 1
 
+# Batch augmentation (csrc/augment.hip): additive exports under ABI 17, descriptor entry points like DESCS.  A table of its own: covered by
+# tests/test_gpu_augment.py.  The host copies of the table (table_host, off_host) are CPU tensors: `aug_call` passes their addresses.
+AUGMENT = {"aug_select": AugDesc, "aug_image": AugDesc, "aug_labels": AugDesc}
+AUG_CANDS, AUG_COLS = 11, 40                                                      # MTT_AUG_* of include/mtt_hip.h
+(AUG_H, AUG_W, AUG_SH, AUG_SW, AUG_RESIZED, AUG_FLIP, AUG_NTEST, AUG_CHOSEN) = range(8)
+AUG_CAND_Y, AUG_CAND_X = 8, 19
+(AUG_BRIGHT, AUG_BETA, AUG_FMODE, AUG_CONTRAST, AUG_CALPHA, AUG_SAT, AUG_SALPHA, AUG_HUE, AUG_HDELTA, AUG_SCALE) = range(30, 40)
+AUG_PLAIN, AUG_DEPTH, AUG_NORMALS, AUG_HUMAN_PARTS = 0, 1, 2, 3
+E_BADARG, E_ALIGN, E_UNSUPPORTED = -1, -2, -3                                     # MTT_E_*
+
 # workspace-size queries mtt_<entry>_ws_floats(const desc*) of the entry points whose cross-workgroup reductions go through caller-owned partials
 WS_QUERIES = {"gemm_colsum": GemmDesc, "chan_logits": ChanLogitDesc, "modulate_bwd": ModulateDesc, "ctr_dw": CtrDesc, "attn_msg_bwd": AttnMsgDesc, "loss": LossDesc,
               "chanattn_bwd": ChanAttnDesc, "detloss": DetLossDesc,
               "groupnorm": GnDesc, "dcn_col2im": DcnDesc, "fcos_bbox_post": BboxPostDesc, "fcos3d": Fcos3dDesc}
-EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_fcos3d_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes", "mtt_det_decode_desc_size", "mtt_det_nms_ws_bytes", "mtt_eval_desc_size", "mtt_eval_ws_floats"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA) + list(POSTPROC) + list(EVAL)]
+EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_fcos3d_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes", "mtt_det_decode_desc_size", "mtt_det_nms_ws_bytes", "mtt_eval_desc_size", "mtt_eval_ws_floats"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA) + list(POSTPROC) + list(EVAL)] + ["mtt_aug_desc_size"] + ["mtt_" + n for n in AUGMENT]
 
 _lib = None
 
@@ -370,7 +387,11 @@ def load():
         raise RuntimeError(f"descriptor layout mismatch for EvalDesc: C {lib.mtt_eval_desc_size()} vs ctypes {C.sizeof(EvalDesc)}")
     lib.mtt_eval_ws_floats.restype = C.c_size_t
     lib.mtt_eval_ws_floats.argtypes = [C.POINTER(EvalDesc)]
-    for name, st in list(DESCS.items()) + list(POSTPROC.items()) + list(EVAL.items()):
+    lib.mtt_aug_desc_size.restype = C.c_size_t
+    lib.mtt_aug_desc_size.argtypes = []
+    if lib.mtt_aug_desc_size() != C.sizeof(AugDesc):
+        raise RuntimeError(f"descriptor layout mismatch for AugDesc: C {lib.mtt_aug_desc_size()} vs ctypes {C.sizeof(AugDesc)}")
+    for name, st in list(DESCS.items()) + list(POSTPROC.items()) + list(EVAL.items()) + list(AUGMENT.items()):
         fn = getattr(lib, "mtt_" + name)
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(st), ptr]
@@ -412,6 +433,32 @@ def eval_ws_floats(kind, batch, pixels):
     desc = EvalDesc()
     desc.kind, desc.B, desc.HW = int(kind), int(batch), int(pixels)
     return int(lib.mtt_eval_ws_floats(C.byref(desc)))
+
+
+def aug_call(name, host=(), stream=None, **fields):
+    """mtt_<name> of AUGMENT.  Device tensors in `fields` become device pointers (a CPU tensor raises, as everywhere); the fields named in
+    `host` are the host copies the entry point validates and take CPU tensors.  Returns the status instead of raising on MTT_E_BADARG, so
+    that a caller can tell a refused table from a failed launch; every other non-zero status raises.  stream: torch's current one by default."""
+    lib = load()
+    desc = AugDesc()
+    for k, v in fields.items():
+        if isinstance(v, torch.Tensor):
+            if k in host:
+                if v.is_cuda:
+                    raise RuntimeError(f"{k} is the host copy of the table and must be a CPU tensor")
+                setattr(desc, k, v.data_ptr())
+            else:
+                setattr(desc, k, _addr(v))
+        elif isinstance(v, (list, tuple)):
+            arr = getattr(desc, k)
+            for i, e in enumerate(v):
+                arr[i] = e
+        elif v is not None:
+            setattr(desc, k, v)
+    rc = getattr(lib, "mtt_" + name)(C.byref(desc), _stream() if stream is None else stream)
+    if rc != 0 and rc != E_BADARG:
+        raise RuntimeError(f"mtt_{name} failed with status {rc}" + (" (argument error)" if rc < 0 else " (hipError_t)"))
+    return rc
 
 
 def dtype_code(t):
