@@ -862,6 +862,50 @@ int mtt_aug_select(const mtt_aug_desc* d, void* stream);
 int mtt_aug_image(const mtt_aug_desc* d, void* stream);
 int mtt_aug_labels(const mtt_aug_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Cityscapes-3D batch preparation on the device (additive exports, ABI 17 unchanged): the per-sample work of the reference's dataset
+ * class (TaskPrompter/data/cityscapes3d.py:137-241) on a batch of equally sized frames.  Both entry points launch on the caller's
+ * stream, never synchronise and return MTT_E_* without launching anything when the descriptor is refused.
+ *
+ * The resampling rules are Pillow's, and their tables are built on the HOST in doubles (multi-task-transformer_amd/cs3d.py):
+ *   bilinear, 8 bit   per axis bounds int32 [n_out, 2] = (first source index, tap count) and coeff int32 [n_out, ksize], the weights
+ *                     fixed to 22 bits.  One pass is out = clip8((2^21 + sum k_i * p_i) >> 22) in 32-bit integers; the horizontal pass
+ *                     runs first and is rounded to 8 bits before the vertical one.  An axis that keeps its size gets the identity table
+ *                     (ksize 1, coefficient 2^22), which reproduces the pixel exactly.
+ *   nearest           per axis index int32 [n_out], built by Pillow's recurrence xo = 0.5 * in/out; xo += in/out in doubles.
+ * xtab / ytab are device tables, xtab_host / ytab_host their host copies: the entry point validates the HOST copy (xn == w, yn == h,
+ * every index inside the source, bounds non-decreasing, 0 < count <= ksize) and derives the tile's LDS need from it; the kernels clamp
+ * what they read from the DEVICE copy to the same ranges again, so no table content makes them read outside src or their LDS window.
+ *
+ * mtt_cs3d_image   src uint8 [B, H, W, 3] (16-byte aligned), bgr != 0: channel order B, G, R as cv2.imread delivers.  out fp32
+ *   [B, 3, h, w] = ((u8 / 255) - mean) / std with IEEE divisions (ToTensor + Normalize), channels R, G, B.  All four tables NULL:
+ *   h == H and w == W, a streaming kernel (H * W % 16 == 0 and 16-byte aligned pointers: a workgroup moves 4096 pixels through LDS,
+ *   three 16-byte loads and twelve 16-byte stores per thread, a wave's stores contiguous; otherwise one pixel per thread).
+ *   Otherwise both axes carry tables and a workgroup owns MTT_CS3D_TILE_H x MTT_CS3D_TILE_W output pixels: it stages the source rows
+ *   of its window into LDS with 16-byte loads, runs the horizontal pass into LDS as uint8 [row][channel][64], then the vertical pass
+ *   and the normalisation, 4 pixels per thread.  MTT_E_UNSUPPORTED when a tile's window exceeds MTT_CS3D_MAX_ROWS source rows or
+ *   MTT_CS3D_MAX_COLS source columns (a reduction by more than about 11 along y or 80 along x).
+ * mtt_cs3d_labels  src = raw labelIds uint8 [B, H, W], disp = disparity uint16 [B, H, W] or NULL.  xtab / ytab nearest tables or
+ *   NULL (identity: the axis keeps its size).  semseg int64 [B, h, w]: the 256-entry restatement of encode_segmap (void ids -> 255, the
+ *   19 valid ids -> 0..18, everything else kept).  flags int32 [B] is cleared, then flags[b] = 1 when an output pixel of image b is
+ *   neither 255 nor below 19 (integer atomic OR).  out = depth fp32 [B, 1, h, w] (only with disp): d > 0 -> (d - 1) / 256; then 0 ->
+ *   -1 (d == 1 included); then 0 where the RAW label id is 10. */
+#define MTT_CS3D_TILE_H 16
+#define MTT_CS3D_TILE_W 64
+#define MTT_CS3D_MAX_ROWS 208
+#define MTT_CS3D_MAX_COLS 5440
+typedef struct {
+  const uint8_t* src; const uint16_t* disp;
+  const int32_t* xtab; const int32_t* ytab; const int32_t* xtab_host; const int32_t* ytab_host;
+  const int32_t* xcoeff; const int32_t* ycoeff;     /* mtt_cs3d_image: device, [xn, xk] and [yn, yk] */
+  float* out; int64_t* semseg; int32_t* flags;
+  int32_t B, H, W, h, w, xn, yn, xk, yk, bgr;
+  float mean[3], std[3];
+} mtt_cs3d_desc;
+size_t mtt_cs3d_desc_size(void);
+int mtt_cs3d_image(const mtt_cs3d_desc* d, void* stream);
+int mtt_cs3d_labels(const mtt_cs3d_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

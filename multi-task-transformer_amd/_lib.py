@@ -253,6 +253,13 @@ class AugDesc(C.Structure):
                 ("fill", f32), ("mean", f32 * 3), ("std", f32 * 3)]
 
 
+class Cs3dDesc(C.Structure):
+    _fields_ = [("src", ptr), ("disp", ptr), ("xtab", ptr), ("ytab", ptr), ("xtab_host", ptr), ("ytab_host", ptr), ("xcoeff", ptr), ("ycoeff", ptr),
+                ("out", ptr), ("semseg", ptr), ("flags", ptr),
+                ("B", i32), ("H", i32), ("W", i32), ("h", i32), ("w", i32), ("xn", i32), ("yn", i32), ("xk", i32), ("yk", i32), ("bgr", i32),
+                ("mean", f32 * 3), ("std", f32 * 3)]
+
+
 # entry point -> (descriptor struct, size index in mtt_desc_size) ; None = positional-argument entry
 DESCS = {
     "loss_fwd": LossDesc,
@@ -333,11 +340,16 @@ AUG_CAND_Y, AUG_CAND_X = 8, 19
 AUG_PLAIN, AUG_DEPTH, AUG_NORMALS, AUG_HUMAN_PARTS = 0, 1, 2, 3
 E_BADARG, E_ALIGN, E_UNSUPPORTED = -1, -2, -3                                     # MTT_E_*
 
+# Cityscapes-3D batch preparation (csrc/cs3d.hip): additive exports under ABI 17 as well, covered by tests/test_gpu_cs3d.py.  The host
+# copies of the index tables (xtab_host, ytab_host) are CPU tensors: `cs3d_call` passes their addresses.
+CS3D = {"cs3d_image": Cs3dDesc, "cs3d_labels": Cs3dDesc}
+CS3D_TILE_H, CS3D_TILE_W, CS3D_MAX_ROWS, CS3D_MAX_COLS = 16, 64, 208, 5440         # MTT_CS3D_* of include/mtt_hip.h
+
 # workspace-size queries mtt_<entry>_ws_floats(const desc*) of the entry points whose cross-workgroup reductions go through caller-owned partials
 WS_QUERIES = {"gemm_colsum": GemmDesc, "chan_logits": ChanLogitDesc, "modulate_bwd": ModulateDesc, "ctr_dw": CtrDesc, "attn_msg_bwd": AttnMsgDesc, "loss": LossDesc,
               "chanattn_bwd": ChanAttnDesc, "detloss": DetLossDesc,
               "groupnorm": GnDesc, "dcn_col2im": DcnDesc, "fcos_bbox_post": BboxPostDesc, "fcos3d": Fcos3dDesc}
-EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_fcos3d_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes", "mtt_det_decode_desc_size", "mtt_det_nms_ws_bytes", "mtt_eval_desc_size", "mtt_eval_ws_floats"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA) + list(POSTPROC) + list(EVAL)] + ["mtt_aug_desc_size"] + ["mtt_" + n for n in AUGMENT]
+EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_fcos3d_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes", "mtt_det_decode_desc_size", "mtt_det_nms_ws_bytes", "mtt_eval_desc_size", "mtt_eval_ws_floats"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA) + list(POSTPROC) + list(EVAL)] + ["mtt_aug_desc_size"] + ["mtt_" + n for n in AUGMENT] + ["mtt_cs3d_desc_size"] + ["mtt_" + n for n in CS3D]
 
 _lib = None
 
@@ -391,7 +403,11 @@ def load():
     lib.mtt_aug_desc_size.argtypes = []
     if lib.mtt_aug_desc_size() != C.sizeof(AugDesc):
         raise RuntimeError(f"descriptor layout mismatch for AugDesc: C {lib.mtt_aug_desc_size()} vs ctypes {C.sizeof(AugDesc)}")
-    for name, st in list(DESCS.items()) + list(POSTPROC.items()) + list(EVAL.items()) + list(AUGMENT.items()):
+    lib.mtt_cs3d_desc_size.restype = C.c_size_t
+    lib.mtt_cs3d_desc_size.argtypes = []
+    if lib.mtt_cs3d_desc_size() != C.sizeof(Cs3dDesc):
+        raise RuntimeError(f"descriptor layout mismatch for Cs3dDesc: C {lib.mtt_cs3d_desc_size()} vs ctypes {C.sizeof(Cs3dDesc)}")
+    for name, st in list(DESCS.items()) + list(POSTPROC.items()) + list(EVAL.items()) + list(AUGMENT.items()) + list(CS3D.items()):
         fn = getattr(lib, "mtt_" + name)
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(st), ptr]
@@ -458,6 +474,31 @@ def aug_call(name, host=(), stream=None, **fields):
     rc = getattr(lib, "mtt_" + name)(C.byref(desc), _stream() if stream is None else stream)
     if rc != 0 and rc != E_BADARG:
         raise RuntimeError(f"mtt_{name} failed with status {rc}" + (" (argument error)" if rc < 0 else " (hipError_t)"))
+    return rc
+
+
+def cs3d_call(name, stream=None, **fields):
+    """mtt_<name> of CS3D.  Device tensors become device pointers (a CPU tensor raises); xtab_host / ytab_host take CPU tensors.  Returns 0 or a negative MTT_E_* status (a refused descriptor, nothing
+    launched); a hipError_t raises."""
+    lib = load()
+    desc = Cs3dDesc()
+    for k, v in fields.items():
+        if isinstance(v, torch.Tensor):
+            if k in ("xtab_host", "ytab_host"):
+                if v.is_cuda:
+                    raise RuntimeError(f"{k} is the host copy of the table and must be a CPU tensor")
+                setattr(desc, k, v.data_ptr())
+            else:
+                setattr(desc, k, _addr(v))
+        elif isinstance(v, (list, tuple)):
+            arr = getattr(desc, k)
+            for i, e in enumerate(v):
+                arr[i] = e
+        elif v is not None:
+            setattr(desc, k, v)
+    rc = getattr(lib, "mtt_" + name)(C.byref(desc), _stream() if stream is None else stream)
+    if rc > 0:
+        raise RuntimeError(f"mtt_{name} failed with status {rc} (hipError_t)")
     return rc
 
 
