@@ -1,5 +1,5 @@
 """Launch census of one training step on the CPU emulator: every aten op that would be a device kernel and every C-ABI call, grouped by
-the product source line that issued it.  Test infrastructure (uses oracle/abi_emul as the library); run from the repo root:
+the product source line that issued it.  Test infrastructure (tests/replay_util.record routes the calls to oracle/abi_emul); run from the repo root:
     python tests/launch_census.py [config=mini_ctr] [prec=bf16]
 """
 import collections
@@ -15,6 +15,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import conftest  # noqa: E402
 import mtt_amd  # noqa: E402
+import replay_util  # noqa: E402
 from oracle import abi_emul, configs, weights  # noqa: E402
 
 PKG = os.path.join(ROOT, "multi-task-transformer_amd")
@@ -53,14 +54,13 @@ def main():
     prec = sys.argv[2] if len(sys.argv) > 2 else "bf16"
     calls = collections.Counter()
 
-    def call(entry, *a, **k):
+    def forward(entry, **k):          # what replay_util.record forwards every call to: count it by source line, hide the emulator's own torch ops
         calls[(entry, site())] += 1
         INSIDE[0] += 1
         try:
-            return abi_emul.call(entry, *a, **k)
+            return abi_emul.call(entry, **k)
         finally:
             INSIDE[0] -= 1
-    mtt_amd.ops.call = call
     cfg = configs.taskprompter(name)
     meta, _ = conftest.load_golden(name)
     sd = weights.synth_state_dict(meta["contract"], 0)
@@ -70,15 +70,22 @@ def main():
     from tests.golden.make_golden import loss_of
     opt = mtt_amd.optim.FusedClipAdam(model.parameters(), lr=1e-4, max_norm=10.0)
     x = weights.synth_images(2, cfg["img_size"], 2)
-    for it in range(2):                       # the second step is the steady state (packs rebuilt after the optimizer ran)
+    census = []
+
+    def step(_=None):
         calls.clear()
         with Census() as c:
             opt.zero_grad()
             out = model(x)
             loss_of(out).backward()
             opt.step()
+        census.append(c)
+    # the second step is the steady state (packs rebuilt after the optimizer ran); no snapshots, only the routing
+    rec = replay_util.record(step, keep_per_signature=0, warmup=step, forward=forward)
+    c = census[-1]
     tot_ops, tot_calls = sum(c.ops.values()), sum(calls.values())
-    print(f"# {name} {prec}: {tot_calls} C-ABI calls + {tot_ops} aten ops in step 2  (depth {cfg.get('depth')})")
+    print(f"# {name} {prec}: {tot_calls} C-ABI calls + {tot_ops} aten ops in step 2  (depth {cfg.get('depth')}); "
+          f"{len(rec.signatures)} distinct kernel configurations")
     by_entry = collections.Counter()
     for (e, s), n in calls.items():
         by_entry[e] += n

@@ -65,14 +65,20 @@ def _row_stride(kw, key):
     return 1
 
 
-def _assert_fails(cname, what, kw, tol, pre, emu, written, dev, keys, skip):
-    r = gpu_cases.compare(kw, tol, pre, emu, written, {k: dev[k] for k in keys}, skip)
+def _assert_fails(cname, what, kw, tol, pre, emu, written, dev, keys, skip, slack=None):
+    r = gpu_cases.compare(kw, tol, pre, emu, written, {k: dev[k] for k in keys}, skip, slack)
     assert not r["ok"], f"{cname}: {what} passed the comparator: {r['errs']}"
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
-def test_comparator_passes_the_emulator_and_fails_planted_defects(case):
-    cname, entry, kw, tol = case
+def check_comparator(cname, entry, kw, tol, zeros_allowed=None, slack_of=None, split_moves=True):
+    """The body of the meta-test for one case: the comparator passes the emulator's own copy and one-ulp bf16 moves, and fails D1 - D4.
+    zeros_allowed: None = the sentinel rule of the hand-written cases (no zero outside the written set of a storage the emulator
+    writes); a dict {argument label: count} = exactly these zeros are there (the replayed calls: tests/replay_util.py refills the
+    others and names the ones the emulator reads).  slack_of: {argument label: compare's slack for that storage} (the replayed calls'
+    named zero-sum outputs, replay_util.ZERO_SUM_OUTPUTS); D1 there, and nowhere else, moves the element by twice the slack more.  split_moves=False leaves the hi planes of split pairs out of the
+    one-ulp moves (D1 - D4 still run on them): the lo value that compensates a moved hi carries a bf16 rounding of 2^-9 |lo|, about
+    2^-17 |x|, which the fp32-class element bound (coef * rms + 4 fp32 ulps of x) admits under the Gaussian fills of the hand-written cases
+    (max / rms < 5) and not at the models' largest activations (max / rms > 20)."""
     kw, pre, emu, written, dev, skip = _emulate(entry, kw)
     assert written, f"{cname}: the emulator wrote nothing"
     names = {}
@@ -82,11 +88,13 @@ def test_comparator_passes_the_emulator_and_fails_planted_defects(case):
     for key, m in written.items():
         if key not in skip:
             zeros = (pre[key] == 0) & ~m
-            assert not zeros.any(), f"{cname}: {names[key]} holds {int(zeros.sum())} zeros outside the written set (fill it with a sentinel)"
+            allowed = (zeros_allowed or {}).get(names[key], 0)
+            assert int(zeros.sum()) == allowed, f"{cname}: {names[key]} holds {int(zeros.sum())} zeros outside the written set, {allowed} named (fill it with a sentinel)"
     for key, p in pre.items():           # and no emulator write leaves a NaN
         assert torch.isfinite(emu[key].double()).all() or not torch.isfinite(p.double()).all(), (cname, names[key])
 
-    r = gpu_cases.compare(kw, tol, pre, emu, written, dev, skip)
+    slack = {key: (slack_of or {}).get(lbl, 0.0) for key, lbl in names.items()}
+    r = gpu_cases.compare(kw, tol, pre, emu, written, dev, skip, slack)
     assert r["ok"], f"{cname}: the emulator's own copy fails: {r['errs']}"
     assert r["errs"]["worst_elem"][0] == 0.0, (cname, r["errs"]["worst_elem"])
 
@@ -98,7 +106,7 @@ def test_comparator_passes_the_emulator_and_fails_planted_defects(case):
     # one-ulp moves of 10 % of the written bf16 elements (split pairs: hi moved, lo compensating, the sum unchanged to bf16 rounding)
     moved = {k: v.clone() for k, v in dev.items()}
     for key, m in written.items():
-        if key in skip or key in lo_planes or dev[key].dtype != torch.bfloat16:
+        if key in skip or key in lo_planes or dev[key].dtype != torch.bfloat16 or (key in partner and not split_moves):
             continue
         pos = m.nonzero()[:, 0]
         pos = pos[torch.rand(pos.numel(), generator=gen) < 0.1]
@@ -109,7 +117,7 @@ def test_comparator_passes_the_emulator_and_fails_planted_defects(case):
         if key in partner:
             lo = moved[partner[key]]
             lo[pos] = (lo[pos].double() + old.double() - moved[key][pos].double()).to(torch.bfloat16)
-    r = gpu_cases.compare(kw, tol, pre, emu, written, moved, skip)
+    r = gpu_cases.compare(kw, tol, pre, emu, written, moved, skip, slack)
     assert r["ok"], f"{cname}: one-ulp bf16 moves fail: {r['errs']}"
 
     frac = _d1_fraction(cname, tol)
@@ -125,7 +133,7 @@ def test_comparator_passes_the_emulator_and_fails_planted_defects(case):
             p = int(free[torch.randint(free.numel(), (1,), generator=gen)])
             old = g[p].clone()
             gpu_cases._bits(g)[p] ^= 1
-            _assert_fails(cname, f"D2 (stray write at {names[key]}[{p}])", kw, tol, pre, emu, written, dev, keys, skip)
+            _assert_fails(cname, f"D2 (stray write at {names[key]}[{p}])", kw, tol, pre, emu, written, dev, keys, skip, slack)
             g[p] = old
         if pos.numel() == 0:
             continue
@@ -137,14 +145,14 @@ def test_comparator_passes_the_emulator_and_fails_planted_defects(case):
             s = float(emu[key][m].double().square().mean().sqrt())
         p = int(pos[torch.randint(pos.numel(), (1,), generator=gen)])
         e = g[p].double()
-        delta = frac * s if s > 0 else 2.0 ** -126
+        delta = (frac * s if s > 0 else 2.0 ** -126) + 2.0 * slack.get(partner[key] if key in lo_planes else key, 0.0)
         if not g.is_floating_point():
             delta = max(delta, 1.0)                 # an integer storage (NMS keep / num_out): the smallest move there is
         if g.dtype == torch.bfloat16 and key not in lo_planes:
             delta += 3 * float(gpu_cases.ulp_bf16(e.reshape(1)))
         old = g[p].clone()
         g[p] = (e + delta).to(g.dtype)
-        _assert_fails(cname, f"D1 ({names[key]}[{p}] moved by {delta:.3g}, s = {s:.3g})", kw, tol, pre, emu, written, dev, keys, skip)
+        _assert_fails(cname, f"D1 ({names[key]}[{p}] moved by {delta:.3g}, s = {s:.3g})", kw, tol, pre, emu, written, dev, keys, skip, slack)
         g[p] = old
         # D3: a run of 16 written elements replaced by those one row stride further on (or back, at the end of the storage)
         rs = _row_stride(kw, key)
@@ -154,7 +162,7 @@ def test_comparator_passes_the_emulator_and_fails_planted_defects(case):
         if (src >= 0).all() and not torch.equal(g[src], g[run]):
             old = g[run].clone()
             g[run] = g[src]
-            _assert_fails(cname, f"D3 ({names[key]}[{int(run[0])}..] from one row stride {rs} away)", kw, tol, pre, emu, written, dev, keys, skip)
+            _assert_fails(cname, f"D3 ({names[key]}[{int(run[0])}..] from one row stride {rs} away)", kw, tol, pre, emu, written, dev, keys, skip, slack)
             g[run] = old
         # D4: the lo value of the element with the largest |hi| zeroed (among those whose lo is at least half its possible size, 2^-10 |hi|:
         # a smaller lo can sit below an fp32-class bound)
@@ -166,8 +174,13 @@ def test_comparator_passes_the_emulator_and_fails_planted_defects(case):
             if p >= 0:
                 old = lo[p].clone()
                 lo[p] = 0
-                _assert_fails(cname, f"D4 ({names[key]}[{p}] lo zeroed)", kw, tol, pre, emu, written, dev, keys, skip)
+                _assert_fails(cname, f"D4 ({names[key]}[{p}] lo zeroed)", kw, tol, pre, emu, written, dev, keys, skip, slack)
                 lo[p] = old
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_comparator_passes_the_emulator_and_fails_planted_defects(case):
+    check_comparator(*case)
 
 
 def test_every_entry_point_is_covered():
