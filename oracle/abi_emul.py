@@ -1486,7 +1486,184 @@ def fcos_bbox_post_bwd(**kw):
         _wr(kw["dscales"], torch.arange(4), ds)
 
 
-_TABLE = dict(gather_rows=gather_rows, winattn_fwd=winattn_fwd, winattn_bwd=winattn_bwd, chanattn_fwd=chanattn_fwd, conv3s2_nchw=conv3s2_nchw, gemm=gemm, upconv4_expand=upconv4_expand, upconv4_gather=upconv4_gather, attn_fwd=attn_fwd, softmax_fwd=softmax_fwd, softmax_bwd=softmax_bwd,
+# ---------------------------------------------------------------------------------------------------------------------------
+# ABI 15: the FCOS3D criterion.  Written from the contract in include/mtt_hip.h: the assignment (everything discrete: which gt a point
+# takes, its label, the direction bin) in fp32 in the reference's operation order, so `label` is exact, `target` is the fp32 quotient and
+# `centerness` torch.exp of the fp32 argument; the loss terms, the division by the counts and the backward (autograd over the fp64
+# restatement of the forward) in fp64.  `ws` is ignored.
+_FCOS3D_BIG = 1e8
+_FCOS3D_KEYS = 9
+
+
+def _f32(v):
+    return torch.tensor(v, dtype=torch.float32)
+
+
+def _fcos3d_points(kw):
+    """-> (level of every point [P], index inside its level [P], xs, ys fp32 [P])"""
+    nlev = int(kw["nlev"])
+    H, W = [int(v) for v in kw["H"][:nlev]], [int(v) for v in kw["W"][:nlev]]
+    lvl = torch.cat([torch.full((H[l] * W[l],), l, dtype=torch.long) for l in range(nlev)])
+    q = torch.cat([torch.arange(H[l] * W[l]) for l in range(nlev)])
+    assert lvl.numel() == int(kw["P"]), "P is the sum of the level sizes"
+    Wp = torch.tensor(W)[lvl]
+    stride, half = _f32(kw["stride"][:nlev])[lvl], _f32(kw["half"][:nlev])[lvl]
+    xs = (q % Wp).float() * stride + half
+    ys = (q // Wp).float() * stride + half
+    return lvl, q, xs, ys
+
+
+def _fcos3d_image_table(kw):
+    n_lab, B = int(kw["n_lab"]), int(kw["B"])
+    img = _rd(kw["img"], torch.arange(3 * n_lab + B)).long()
+    return img[:n_lab], img[n_lab:2 * n_lab], img[2 * n_lab:3 * n_lab], img[3 * n_lab:]
+
+
+def _fcos3d_assign(kw):
+    """label int64 [n_lab, P], target fp32 [n_lab, 13, P], centerness fp32 [n_lab, P] of the contract"""
+    n_lab, C, P, nlev = int(kw["n_lab"]), int(kw["C"]), int(kw["P"]), int(kw["nlev"])
+    lvl, _, xs, ys = _fcos3d_points(kw)
+    stride, rad = _f32(kw["stride"][:nlev])[lvl], _f32(kw["radius"][:nlev])[lvl]
+    lo, hi = _f32(kw["rr_lo"][:nlev])[lvl][:, None], _f32(kw["rr_hi"][:nlev])[lvl][:, None]
+    goff, gcnt, _, _ = _fcos3d_image_table(kw)
+    label = torch.full((n_lab, P), C, dtype=torch.int64)
+    target = torch.zeros(n_lab, 13, P, dtype=torch.float32)
+    cen = torch.zeros(n_lab, P, dtype=torch.float32)
+    ctr_alpha = _f32(float(kw["ctr_alpha"]))
+    for k in range(n_lab):
+        n = int(gcnt[k])
+        if n == 0:                                                       # labelled, no gts: label C, zero targets, zero centerness
+            continue
+        rec = _rd(kw["gts"], (int(goff[k]) + torch.arange(n))[:, None] * 16 + torch.arange(16)[None, :]).float()      # [n, 16]
+        X, Y, R = xs[:, None], ys[:, None], rad[:, None]
+        cx, cy = rec[None, :, 5], rec[None, :, 6]
+        dx, dy = X - cx, Y - cy
+        left, top, right, bottom = X - rec[None, :, 0], Y - rec[None, :, 1], rec[None, :, 2] - X, rec[None, :, 3] - Y
+        cb = torch.minimum(torch.minimum(X - (cx - R), Y - (cy - R)), torch.minimum((cx + R) - X, (cy + R) - Y))
+        mx = torch.maximum(torch.maximum(left, top), torch.maximum(right, bottom))
+        ok = (cb > 0) & (mx >= lo) & (mx <= hi)
+        dist = torch.where(ok, torch.sqrt(dx * dx + dy * dy), torch.full_like(dx, _FCOS3D_BIG))
+        best = dist.min(1)[0]
+        # the FIRST gt among those at the smallest distance (gt 0 when every distance is 1e8)
+        sel = torch.where(dist == best[:, None], torch.arange(n)[None, :].expand(P, n), torch.full((P, n), n)).min(1)[0]
+        ar = torch.arange(P)
+        label[k] = torch.where(best == _FCOS3D_BIG, torch.full((P,), C, dtype=torch.int64), rec[sel, 4].long())
+        sdx, sdy = dx[ar, sel], dy[ar, sel]
+        cols = [sdx / stride, sdy / stride, rec[sel, 7]] + [rec[sel, 8 + c] for c in range(6)] + \
+               [left[ar, sel] / stride, top[ar, sel] / stride, right[ar, sel] / stride, bottom[ar, sel] / stride]
+        target[k] = torch.stack(cols, 0)
+        rel = torch.sqrt(sdx * sdx + sdy * sdy) / (_f32(1.414) * rad)
+        cen[k] = torch.exp(-ctr_alpha * rel)
+    return label, target, cen
+
+
+def _fcos3d_wr_assign(kw, label, target, cen):
+    _wr(kw["label"], torch.arange(label.numel()), label.reshape(-1))
+    _wr(kw["target"], torch.arange(target.numel()), target.reshape(-1))
+    _wr(kw["centerness"], torch.arange(cen.numel()), cen.reshape(-1))
+
+
+def fcos3d_targets(**kw):
+    _fcos3d_wr_assign(kw, *_fcos3d_assign(kw))
+
+
+def _fcos3d_map_index(kw, ch):
+    """flat NCHW offsets [B, P, ch] of every (image, point, channel) in the per-level maps, and the level slices of P"""
+    nlev, B = int(kw["nlev"]), int(kw["B"])
+    out, o = [], 0
+    for l in range(nlev):
+        HW = int(kw["H"][l]) * int(kw["W"][l])
+        idx = (torch.arange(B)[:, None, None] * ch + torch.arange(ch)[None, None, :]) * HW + torch.arange(HW)[None, :, None]
+        out.append((slice(o, o + HW), idx))
+        o += HW
+    return out
+
+
+def _fcos3d_read_maps(kw, name, ch):
+    """the level maps kw[name][l] (NCHW fp32) -> [B, P, ch] fp64"""
+    return torch.cat([_rd(kw[name][l], idx) for l, (_, idx) in enumerate(_fcos3d_map_index(kw, ch))], 1)
+
+
+def _fcos3d_components(kw, x, bp, dp, cp, label, target, cen, num_pos, avg):
+    """The eight components (fp64) from the labelled images' predictions x [n, P, C], bp [n, P, 13], dp [n, P, 6], cp [n, P] and the
+    assignment (label int64 [n, P], target fp32 [n, 13, P], centerness fp32 [n, P]); num_pos / avg: the counts they are divided by."""
+    C = int(kw["C"])
+    f = lambda k: float(_f32(float(kw[k])))
+    gamma, alpha, beta, beta2d = f("gamma"), f("alpha"), f("beta"), f("beta2d")
+    lw = [float(v) for v in _f32([float(v) for v in kw["loss_weight"]])]
+    cw = _f32([float(v) for v in kw["code_weight"]]).double()
+    pos = (label >= 0) & (label < C)
+    t = torch.nn.functional.one_hot(label.clamp(0, C), C + 1)[..., :C].double()
+    s = torch.sigmoid(x)
+    pt = (1 - s) * t + s * (1 - t)
+    focal = torch.nn.functional.binary_cross_entropy_with_logits(x, t, reduction="none") * (alpha * t + (1 - alpha) * (1 - t)) * pt.pow(gamma)
+    comps = [lw[0] * focal.sum() / avg]
+    zero = x.sum() * 0
+    if not num_pos > 0:
+        return comps + [zero] * 7
+    tg = target.permute(0, 2, 1)[pos]                                    # [n_pos, 13] fp32
+    p, tgd = bp[pos], tg.double()
+    tr = tgd[:, 6:9]
+    pe = torch.cat([p[:, :6], torch.sin(p[:, 6:9]) * torch.cos(tr), p[:, 9:]], 1)
+    te = torch.cat([tgd[:, :6], torch.cos(p[:, 6:9]) * torch.sin(tr), tgd[:, 9:]], 1)
+    d = (pe - te).abs()
+    bvec = torch.tensor([beta] * 9 + [beta2d] * 4, dtype=torch.float64)
+    sl1 = torch.where(d < bvec, 0.5 * d * d / bvec, d - 0.5 * bvec) * cw
+    for sl, w in ((slice(0, 2), lw[1]), (slice(2, 3), lw[1]), (slice(3, 6), lw[1]), (slice(6, 9), lw[1])):
+        comps.append(w * sl1[:, sl].sum() / num_pos)
+    # the direction bin, decided in fp32: floor(limit_period(rot - dir_offset, 0, 2 pi) / pi) clamped to {0, 1}
+    rot = tg[:, 6:9] - _f32(float(kw["dir_offset"]))
+    two_pi, pi = _f32(2 * math.pi), _f32(math.pi)
+    lp = rot - torch.floor(rot / two_pi + 0) * two_pi
+    bins = torch.floor(lp / pi).long().clamp(0, 1)
+    dpos = dp[pos].view(-1, 3, 2)
+    ce = torch.logsumexp(dpos, -1) - torch.gather(dpos, 2, bins[:, :, None])[..., 0]          # [n_pos, 3]
+    comps.append(sum(lw[2] * ce[:, r].sum() / num_pos for r in range(3)))
+    xc, ct = cp[pos], cen[pos].double()
+    comps.append(lw[3] * (torch.nn.functional.softplus(xc) - xc * ct).sum() / num_pos)
+    comps.append(lw[4] * sl1[:, 9:].sum() / num_pos)
+    return comps
+
+
+def _fcos3d_labelled(kw, maps):
+    _, _, bidx, _ = _fcos3d_image_table(kw)
+    return [m[bidx] for m in maps]
+
+
+def fcos3d_loss_fwd(**kw):
+    label, target, cen = _fcos3d_assign(kw)
+    _fcos3d_wr_assign(kw, label, target, cen)
+    C, n_lab = int(kw["C"]), int(kw["n_lab"])
+    maps = [_fcos3d_read_maps(kw, n, ch) for n, ch in (("cls", C), ("bbox", 13), ("dir", 6), ("ctr", 1))]
+    x, bp, dp, cp = _fcos3d_labelled(kw, maps)
+    num_pos = float(((label >= 0) & (label < C)).sum())
+    comps = _fcos3d_components(kw, x, bp, dp, cp[..., 0], label, target, cen, num_pos, num_pos + n_lab)
+    out = torch.stack([c.double() for c in comps])
+    _wr(kw["out"], torch.arange(9), torch.cat([out, out.sum()[None]]))
+    _wr(kw["stats"], torch.arange(2), torch.tensor([num_pos, num_pos + n_lab], dtype=torch.float64))
+
+
+def fcos3d_loss_bwd(**kw):
+    """autograd over the fp64 restatement; label / target / centerness / stats are read back as the forward stored them"""
+    C, n_lab, P = int(kw["C"]), int(kw["n_lab"]), int(kw["P"])
+    label = _rd(kw["label"], torch.arange(n_lab * P)).long().view(n_lab, P)
+    target = _rd(kw["target"], torch.arange(n_lab * 13 * P)).float().view(n_lab, 13, P)
+    cen = _rd(kw["centerness"], torch.arange(n_lab * P)).float().view(n_lab, P)
+    num_pos, avg = (float(v) for v in _rd(kw["stats"], torch.arange(2)))
+    gout = _rd(kw["gout"], torch.arange(9))
+    spec = (("cls", "dcls", C), ("bbox", "dbbox", 13), ("dir", "ddir", 6), ("ctr", "dctr", 1))
+    leaves = [_fcos3d_read_maps(kw, n, ch).requires_grad_(True) for n, _, ch in spec]
+    x, bp, dp, cp = _fcos3d_labelled(kw, leaves)
+    comps = _fcos3d_components(kw, x, bp, dp, cp[..., 0], label, target, cen, num_pos, avg)
+    total = sum((gout[i] + gout[8]) * c for i, c in enumerate(comps))
+    grads = torch.autograd.grad(total, leaves, allow_unused=True)
+    for (_, dn, ch), leaf, g in zip(spec, leaves, grads):
+        g = torch.zeros_like(leaf) if g is None else g
+        for l, (sl, idx) in enumerate(_fcos3d_map_index(kw, ch)):
+            _wr(kw[dn][l], idx.reshape(-1), g[:, sl].reshape(-1))
+
+
+_TABLE = dict(fcos3d_targets=fcos3d_targets, fcos3d_loss_fwd=fcos3d_loss_fwd, fcos3d_loss_bwd=fcos3d_loss_bwd, gather_rows=gather_rows, winattn_fwd=winattn_fwd, winattn_bwd=winattn_bwd, chanattn_fwd=chanattn_fwd, conv3s2_nchw=conv3s2_nchw, gemm=gemm, upconv4_expand=upconv4_expand, upconv4_gather=upconv4_gather, attn_fwd=attn_fwd, softmax_fwd=softmax_fwd, softmax_bwd=softmax_bwd,
               layernorm_fwd=layernorm_fwd, layernorm_bwd=layernorm_bwd, chan_logits=chan_logits, modulate=modulate,
               ctr_mix=ctr_mix, bilinear_fwd=bilinear_fwd, bilinear_bwd=bilinear_bwd, bn_stats=bn_stats,
               bn_apply=bn_apply, bn_bwd_reduce=bn_bwd_reduce, bn_bwd_apply=bn_bwd_apply,
@@ -1502,7 +1679,7 @@ _POS = dict(boxes_overlap_bev=boxes_overlap_bev, nms_bev=nms_bev, patchify=patch
 
 
 def call(name, **kw):
-    with torch.enable_grad() if name in ("dwconv3x3s2_bwd", "avgpool_ceil_bwd", "loss_bwd", "upconv4_gather", "winattn_bwd", "chanattn_bwd", "conv3s2_nchw_bwd", "ctr_weights_bwd", "detloss_bwd") else torch.no_grad():
+    with torch.enable_grad() if name in ("dwconv3x3s2_bwd", "avgpool_ceil_bwd", "loss_bwd", "upconv4_gather", "winattn_bwd", "chanattn_bwd", "conv3s2_nchw_bwd", "ctr_weights_bwd", "detloss_bwd", "fcos3d_loss_bwd") else torch.no_grad():
         if name in _POS:
             return _POS[name](kw["args"])
         return _TABLE[name](**kw)

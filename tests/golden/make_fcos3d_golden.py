@@ -112,7 +112,7 @@ def _gt(box, label, ci, g):
                 rotation_S=(torch.rand(n, 3, generator=g) * 2 - 1) * 3.1, center_I=torch.tensor(ci, dtype=torch.float32))
 
 
-def _random_gts(n, H, W, g, off_image=False):
+def _random_gts(n, H, W, g, off_image=False, num_classes=6):
     wh = torch.rand(n, 2, generator=g) * torch.tensor([W * 0.5, H * 0.5]) + 6.0
     c = torch.rand(n, 2, generator=g) * torch.tensor([W, H])
     if off_image:
@@ -120,14 +120,16 @@ def _random_gts(n, H, W, g, off_image=False):
     x1y1 = c - wh * (0.3 + 0.4 * torch.rand(n, 2, generator=g))
     box = torch.cat([x1y1, x1y1 + wh], 1)
     ci = torch.cat([c, torch.rand(n, 1, generator=g) * 50 + 2], 1)
-    return _gt(box.tolist(), torch.randint(0, 6, (n,), generator=g).tolist(), ci.tolist(), g)
+    return _gt(box.tolist(), torch.randint(0, num_classes, (n,), generator=g).tolist(), ci.tolist(), g)
 
 
-def case_a_labels(strides, g):
+def case_a_labels(strides, g, radius=1.5, range_end=96.0, num_classes=6):
+    """the hand-made gts of case a; radius = center_sample_radius, range_end = the upper end of level 0's regress range, the labels
+    folded into num_classes"""
     s0 = np.float32(strides[0])
     half = np.float32(strides[0] // 2)
     xs = lambda i: np.float32(np.float32(i) * s0) + half                # level-0 point coordinates, as get_points computes them
-    rad = np.float32(strides[0] * 1.5)
+    rad = np.float32(strides[0] * radius)
     box, lab, ci = [], [], []
     # two gts with one centre: every point ties, the first wins (the second is taken by no point)
     box += [[30.0, 20.0, 100.0, 80.0], [34.0, 22.0, 96.0, 78.0]]; lab += [2, 4]; ci += [[64.0, 48.0, 20.0], [64.0, 48.0, 30.0]]
@@ -140,30 +142,46 @@ def case_a_labels(strides, g):
     box += [[float(a) - 20, float(y6) - 15, float(a) + 20, float(y6) + 15], [float(b) - 20, float(y6) - 15, float(b) + 20, float(y6) + 15]]
     lab += [1, 3]; ci += [[float(a), float(y6), 11.0], [float(b), float(y6), 12.0]]
     # the point (4, 1) exactly on the left edge of a centre-sampling box: cx - radius == xs
-    cx = np.float32(xs(4) + rad)
-    while np.float32(cx - rad) != xs(4):
-        cx = np.nextafter(cx, np.float32(np.inf), dtype=np.float32)
+    # (the first point of 4, 5, 3, 6, ... and the first centre, upwards then downwards from xs + radius, for which the fp32 difference is
+    # exact: not every radius has one at point 4; the cs set does, at or above xs + radius)
+    for bx in (4, 5, 3, 6, 2, 7):
+        for step in (np.float32(np.inf), np.float32(-np.inf)):
+            cx = np.float32(xs(bx) + rad)
+            for _ in range(16):
+                if np.float32(cx - rad) == xs(bx):
+                    break
+                cx = np.nextafter(cx, step, dtype=np.float32)
+            if np.float32(cx - rad) == xs(bx):
+                break
+        if np.float32(cx - rad) == xs(bx):
+            break
+    assert np.float32(cx - rad) == xs(bx)
     y1 = xs(1)
     box += [[float(cx) - 25, float(y1) - 12, float(cx) + 25, float(y1) + 12]]; lab += [0]; ci += [[float(cx), float(y1) + 3.0, 7.0]]
-    # the point (8, 8) exactly on the upper end of level 0's regress range: max(l, t, r, b) == 96
+    # the point (8, 8) exactly on the upper end of level 0's regress range: max(l, t, r, b) == range_end (96 in the cs set)
     x8 = xs(8)
-    x1 = np.float32(x8 - np.float32(96.0))
-    assert np.float32(x8 - x1) == np.float32(96.0)
+    x1 = np.float32(x8 - np.float32(range_end))
+    assert np.float32(x8 - x1) == np.float32(range_end)
     box += [[float(x1), float(xs(8)) - 30, float(x8) + 40, float(xs(8)) + 30]]; lab += [5]; ci += [[float(x8) + 2.0, float(xs(8)) - 2.0, 9.0]]
     # centred off the image: no point takes it
     box += [[-400.0, 10.0, -200.0, 60.0]]; lab += [1]; ci += [[-300.0, 35.0, 30.0]]
-    return _gt(box, lab, ci, g), dict(mirror_x=i, boundary_cx=float(cx), range_x1=float(x1))
+    return _gt(box, [l % num_classes for l in lab], ci, g), dict(mirror_x=i, boundary_cx=float(cx), range_x1=float(x1),
+                                                                  **({} if bx == 4 else dict(boundary_x=bx)))
 
 
-def make_labels(case, strides, g):
+def make_labels(case, strides, g, params=None):
+    """params: the parameter set the hand-made boundaries and the label range of cases a / b come from (None: the cs values)"""
     H, W = 110.0, 215.0
     info = {}
+    geo = {} if params is None else dict(radius=params['center_sample_radius'], range_end=float(params['regress_ranges'][0][1]),
+                                         num_classes=params['num_classes'])
+    nc = geo.get('num_classes', 6)
     if case == 'a':
-        e0, info = case_a_labels(strides, g)
-        dl = [e0, _random_gts(3, H, W, g), _random_gts(5, H, W, g)]
+        e0, info = case_a_labels(strides, g, **geo)
+        dl = [e0, _random_gts(3, H, W, g, num_classes=nc), _random_gts(5, H, W, g, num_classes=nc)]
         num = [len(dl[0]['label']), 0, 5]
     elif case == 'b':
-        dl = [_random_gts(3, 64, 128, g, off_image=True), _random_gts(2, 64, 128, g, off_image=True)]
+        dl = [_random_gts(3, 64, 128, g, off_image=True, num_classes=nc), _random_gts(2, 64, 128, g, off_image=True, num_classes=nc)]
         num = [3, 2]
     elif case == 'c':
         dl = [_random_gts(2, 64, 128, g), _random_gts(1, 64, 128, g)]
@@ -176,8 +194,8 @@ def make_labels(case, strides, g):
     return labels, info
 
 
-def random_preds(B, levels, g):
-    return [[torch.randn(B, c, h, w, generator=g) * (2.0 if k == 0 else 1.0) for (h, w) in levels] for k, c in enumerate(NCH)]
+def random_preds(B, levels, g, nch=NCH):
+    return [[torch.randn(B, c, h, w, generator=g) * (2.0 if k == 0 else 1.0) for (h, w) in levels] for k, c in enumerate(nch)]
 
 
 def reference_targets(crit, labels, featmap_sizes):
@@ -286,12 +304,70 @@ def generate():
     return meta, out
 
 
-def main(out_dir=HERE):
-    meta, arrays = generate()
-    with open(os.path.join(out_dir, "fcos3d.json"), "w") as f:
-        json.dump(meta, f, indent=0, sort_keys=True)
-    np.savez_compressed(os.path.join(out_dir, "fcos3d.npz"), **arrays)
+# The alt parameter set: nothing coincides (the cs set has gamma 2, beta == beta2d, loss weights (5, 1, 1, 1, 1), dir_offset 0), so an
+# index, a beta or a sign mixed up in the kernels or in DetModel._desc changes an asserted number.  gamma >= 1: below 1 the reference's
+# own gradient is NaN at saturated logits.  Both betas are large enough that N(0, 1) predictions fill the quadratic smooth-L1 branch.
+ALT = dict(num_classes=3, center_sample_radius=2.0, centerness_alpha=1.7, dir_offset=0.7854,
+           loss_cls=dict(type='FocalLoss', use_sigmoid=True, gamma=1.5, alpha=0.4, loss_weight=3.0),
+           loss_bbox=dict(type='SmoothL1Loss', beta=0.5, loss_weight=1.3),
+           loss_dir=dict(type='CrossEntropyLoss', use_sigmoid=False, loss_weight=0.7),
+           loss_centerness=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.9),
+           loss_bbox2d=dict(type='SmoothL1Loss', beta=2.0, loss_weight=0.45),
+           code_weight=[1.0, 0.9, 0.2, 1.1, 1.2, 0.8, 5.0, 4.0, 3.0, 0.7, 0.6, 1.4, 1.5])
+ALT_GOUT = (0.7, -1.3, 2.1, 0.4, -0.9, 1.6, -2.4, 3.2, 0.55)         # upstream gradient of (the eight components, loss_sum)
+
+
+def alt_params(dhp):
+    p = plain(cs_params(dhp))
+    p.update(json.loads(json.dumps(ALT)))
+    return p
+
+
+def generate_alt():
+    """fcos3d_alt.*: cases a (the geometry of fcos3d.* a: ties, boundary points, the middle image unlabelled) and b (num_pos == 0) under
+    the alt parameter set; one gradient set per case, d (sum_i w_i * component_i + w_8 * loss_sum) / d every pred map, w = ALT_GOUT"""
+    torch.set_num_threads(1)
+    det_model, dhp = reference()
+    params = alt_params(dhp)
+    C = params['num_classes']
+    meta = dict(params=params, img_ds_ratio=IMG_DS_RATIO, keys=list(KEYS), gout=list(ALT_GOUT), cases={})
+    out = {}
+    for name, levels in (('a', LEVELS_A), ('b', LEVELS_B)):
+        g = torch.Generator().manual_seed(1000 + ord(name))
+        labels, info = make_labels(name, params['strides'], g, params)
+        B = len(labels['det_labels'])
+        preds = random_preds(B, levels, g, (C, 13, 6, 1))
+        leaves = [[p.clone().requires_grad_(True) for p in lst] for lst in preds]
+        crit = det_model.DetModel(**json.loads(json.dumps(params)))
+        ld, ls = crit.loss(tuple(list(lst) for lst in leaves), labels)
+        assert sorted(ld) == sorted(KEYS)                               # (the num_pos == 0 branch orders them differently)
+        total = sum(w * ld[k] for w, k in zip(ALT_GOUT, KEYS)) + ALT_GOUT[8] * ls
+        flat = [p for lst in leaves for p in lst]
+        grads = torch.autograd.grad(total, flat, allow_unused=True)
+        lab, tgt, ctr = reference_targets(crit, labels, levels)
+        pos = (lab >= 0) & (lab < C)
+        store_labels(out, name, labels)
+        for j, (p, gr) in enumerate(zip(flat, grads)):
+            out[f"{name}/pred{j}"] = p.detach().numpy()
+            out[f"{name}/grad{j}"] = (torch.zeros_like(p) if gr is None else gr).numpy()
+        out[f"{name}/labels"] = lab.numpy().astype(np.int8)
+        out[f"{name}/pos_targets"] = tgt[pos].numpy()
+        out[f"{name}/pos_ctr"] = ctr[pos].numpy()
+        meta['cases'][name] = dict(B=B, levels=[list(l) for l in levels], loss={k: float(v) for k, v in ld.items()}, loss_keys=list(ld.keys()),
+                                   loss_sum=float(ls), info=info, num_pos=int(pos.sum()))
+    return meta, out
+
+
+def main(out_dir=HERE, which=("cs", "alt")):
+    for tag, gen, stem in (("cs", generate, "fcos3d"), ("alt", generate_alt, "fcos3d_alt")):
+        if tag not in which:
+            continue
+        meta, arrays = gen()
+        with open(os.path.join(out_dir, stem + ".json"), "w") as f:
+            json.dump(meta, f, indent=0, sort_keys=True)
+        np.savez_compressed(os.path.join(out_dir, stem + ".npz"), **arrays)
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else HERE)       # an output directory other than tests/golden: a regeneration check
+    # an output directory other than tests/golden: a regeneration check; a third argument (cs / alt) writes that fixture alone
+    main(sys.argv[1] if len(sys.argv) > 1 else HERE, tuple(sys.argv[2:3]) or ("cs", "alt"))

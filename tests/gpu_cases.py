@@ -221,7 +221,8 @@ def compare(kw, tol, pre, emu, written, dev, skip=(), slack=None, written_norm=F
 
 
 # entry points whose workspace has a size query in the library: entry -> the query's name (mtt_<query>_ws_floats(desc))
-WS_QUERY = {"groupnorm_fwd": "groupnorm", "groupnorm_bwd": "groupnorm", "dcn_col2im_bwd": "dcn_col2im", "fcos_bbox_post_bwd": "fcos_bbox_post"}
+WS_QUERY = {"groupnorm_fwd": "groupnorm", "groupnorm_bwd": "groupnorm", "dcn_col2im_bwd": "dcn_col2im", "fcos_bbox_post_bwd": "fcos_bbox_post",
+            "fcos3d_targets": "fcos3d", "fcos3d_loss_fwd": "fcos3d", "fcos3d_loss_bwd": "fcos3d"}
 
 
 def _device_ws(name, kw, gpu_kw):
@@ -1526,16 +1527,189 @@ def product_config_cases():
     return cases
 
 
+# ---- the FCOS3D criterion (ABI 15, csrc/det_loss3d.hip) ------------------------------------------------------------------------------
+FCOS3D_GEOMETRIES = {
+    # five levels, P = 286: two workgroups of 256 points, four level boundaries inside them, a ragged tail
+    "p286": (((10, 20), (5, 10), (3, 5), (3, 5), (2, 3)), (8.0, 16.0, 32.0, 32.0, 64.0), ((-1, 48), (48, 96), (96, 192), (192, 384), (384, 1e8))),
+    # one level (the level search loops zero times), P = 256 exactly: no tail
+    "one16": (((16, 16),), (8.0,), ((-1, 1e8),)),
+    # eight levels (MTT_FCOS3D_MAX_LEVELS); the first fills a workgroup, so a level boundary falls on the workgroup boundary
+    "eight": (((16, 16), (1, 2), (1, 1), (1, 2), (1, 1), (1, 2), (1, 1), (1, 2)), (8.0, 16.0, 24.0, 32.0, 40.0, 48.0, 56.0, 64.0),
+              ((-1, 40), (40, 60), (60, 80), (80, 100), (100, 120), (120, 140), (140, 160), (160, 1e8))),
+    # a tiny P for the gt counts past one LDS chunk of 128
+    "tiny": (((4, 6), (2, 3)), (8.0, 16.0), ((-1, 24), (24, 1e8))),
+}
+FCOS3D_CS = dict(C=6, radius=1.5, ctr_alpha=2.5, dir_offset=0.0, gamma=2.0, alpha=0.25, beta=1.0 / 9.0, beta2d=1.0 / 9.0,
+                 loss_weight=[5.0, 1.0, 1.0, 1.0, 1.0], code_weight=[1.0, 1.0, 0.2, 1.0, 1.0, 1.0, 5.0, 5.0, 5.0, 1.0, 1.0, 1.0, 1.0])
+FCOS3D_ALT = dict(C=3, radius=2.0, ctr_alpha=1.7, dir_offset=0.7854, gamma=1.5, alpha=0.4, beta=0.5, beta2d=2.0,
+                  loss_weight=[3.0, 1.3, 0.7, 1.9, 0.45], code_weight=[1.0, 0.9, 0.2, 1.1, 1.2, 0.8, 5.0, 4.0, 3.0, 0.7, 0.6, 1.4, 1.5])
+FCOS3D_GOUT = (0.7, -1.3, 2.1, 0.4, -0.9, 1.6, -2.4, 3.2, 0.55)       # nine pairwise-distinct non-zero upstream gradients
+FCOS3D_BATCHES = (
+    # (tag, geometry, parameters, gts per labelled image, B, unlabelled, C override, exercises positives, saturated logits)
+    ("p286_cs_b4", "p286", FCOS3D_CS, (7, 9), 4, (0, 3), None, True, False),
+    ("p286_alt_b4", "p286", FCOS3D_ALT, (8, 7), 4, (0, 3), None, True, False),
+    # cls and ctr logits of +-30 and +-90 at positive and at background points and direction logit pairs 100 apart, in cases of their own:
+    # loss_cls there is 1e4 x the small components, which the rms-relative element bound of `out` then no longer judges
+    ("p286_cs_b4_sat", "p286", FCOS3D_CS, (7, 9), 4, (0, 3), None, True, True),
+    ("p286_alt_b4_sat", "p286", FCOS3D_ALT, (8, 7), 4, (0, 3), None, True, True),
+    ("one16_alt", "one16", FCOS3D_ALT, (9, 8), 2, (), None, True, False),
+    ("eight_alt", "eight", FCOS3D_ALT, (9, 8), 3, (1,), None, True, False),
+    ("p286_alt_gamma1", "p286", dict(FCOS3D_ALT, gamma=1.0), (8, 7), 2, (), None, True, False),
+    ("p286_alt_gamma1_sat", "p286", dict(FCOS3D_ALT, gamma=1.0), (8, 7), 2, (), None, True, True),
+    ("p286_alt_c1", "p286", FCOS3D_ALT, (8, 7), 2, (), 1, True, False),
+    ("p286_cs_c10", "p286", FCOS3D_CS, (8, 7), 2, (), 10, True, False),
+    ("p286_alt_one_empty", "p286", FCOS3D_ALT, (0, 8), 2, (), None, True, False),
+    ("p286_alt_all_empty", "p286", FCOS3D_ALT, (0, 0), 3, (1,), None, False, False),
+    ("tiny_alt_gts128_129_257", "tiny", FCOS3D_ALT, (128, 129, 257), 3, (), None, False, False),
+)
+# names of the cases meant to exercise positives (tests/test_parity_comparator.py asserts their population)
+FCOS3D_POSITIVE_CASES = tuple(f"fcos3d_loss_fwd_{b[0]}" for b in FCOS3D_BATCHES if b[7])
+
+
+def _gapped(vals, gap, pad=37):
+    """vals as a view into a larger storage with `gap` before and after it: a read (inputs, GAP) or write (outputs, a sentinel) past the
+    map shows up"""
+    store = torch.full((vals.numel() + 2 * pad,), gap, dtype=vals.dtype)
+    view = store[pad:pad + vals.numel()].view(vals.shape)
+    view.copy_(vals)
+    return view
+
+
+def _fcos3d_gts(g, n, extent, C, dir_offset, big=()):
+    """n gt records [n, 16] spread over an image of `extent` = (W, H): boxes of mixed sizes around their centres, the rotations of the
+    first gts placed so that rot - dir_offset lands exactly on 0 and on fp32 pi (the direction bin's edges); big: half sizes of square
+    boxes around the image centre that take the place of the last gts (one per higher level: positives there)"""
+    Wd, Hd = extent
+    c = torch.rand(n, 2, generator=g) * torch.tensor([Wd, Hd])
+    wh = torch.rand(n, 2, generator=g) * torch.tensor([Wd * 0.6, Hd * 0.6]) + 6.0
+    x1y1 = c - wh * (0.3 + 0.4 * torch.rand(n, 2, generator=g))
+    rec = torch.zeros(n, 16)
+    if n >= len(big) + 2:
+        for j, h in enumerate(big):
+            c[n - 1 - j] = torch.tensor([Wd / 2 + 3.0 * j, Hd / 2 - 2.0 * j])
+            x1y1[n - 1 - j], wh[n - 1 - j] = c[n - 1 - j] - h, torch.tensor([2.0 * h, 2.0 * h])
+    rec[:, 0:2], rec[:, 2:4] = x1y1, x1y1 + wh
+    rec[:, 4] = torch.randint(0, C, (n,), generator=g).float()
+    rec[:, 5:7], rec[:, 7] = c, torch.rand(n, generator=g) * 50 + 2
+    rec[:, 8:11] = torch.rand(n, 3, generator=g) * 4 + 0.5
+    rec[:, 11:14] = (torch.rand(n, 3, generator=g) * 2 - 1) * 3.1
+    off, pi32 = torch.tensor(dir_offset, dtype=torch.float32), torch.tensor(3.141592653589793, dtype=torch.float32)
+    if n >= 2:
+        rec[0, 11], rec[0, 12] = off, off + pi32
+        rec[1, 12], rec[1, 13] = off, off + pi32
+        if float(off) != 0.0:                                              # the differences land exactly on 0 and on fp32 pi
+            assert float(rec[0, 11] - off) == 0.0 and float(rec[0, 12] - off) == float(pi32)
+    rec[:, 14:] = GAP                                                       # the two unused floats of a record
+    return rec
+
+
+def _fcos3d_case(g, geom, par, counts, B=None, unlabelled=(), extreme=False, C=None):
+    """the descriptor fields of one batch (no outputs): counts = gts per labelled image"""
+    sizes, strides, rr = FCOS3D_GEOMETRIES[geom]
+    par = dict(par, C=C if C is not None else par["C"])
+    L, Cn = len(sizes), par["C"]
+    B = B if B is not None else len(counts) + len(unlabelled)
+    keep = [b for b in range(B) if b not in unlabelled]
+    assert len(keep) == len(counts)
+    P = sum(h * w for h, w in sizes)
+    extent = (sizes[0][1] * strides[0], sizes[0][0] * strides[0])
+    big = [float(r[0]) + 8.0 for r in rr[1:]] if geom == "p286" else []          # in range on level l: half size 8 past the range start
+    recs = [_fcos3d_gts(g, n, extent, Cn, par["dir_offset"], big) for n in counts]
+    offs, o = [], 0
+    for n in counts:
+        offs.append(o)
+        o += n
+    compact = [-1] * B
+    for k, b in enumerate(keep):
+        compact[b] = k
+    gts = torch.cat(recs) if o > 0 else torch.full((1, 16), GAP)           # the dummy record of a batch without gts: never read
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+    pad = lambda v, z: list(v) + [z] * (8 - len(v))
+    kw = dict(H=pad([h for h, _ in sizes], 0), W=pad([w for _, w in sizes], 0), stride=pad([f32(s) for s in strides], 0.0),
+              half=pad([f32(s // 2) for s in strides], 0.0), radius=pad([f32(s * par["radius"]) for s in strides], 0.0),
+              rr_lo=pad([f32(r[0]) for r in rr], 0.0), rr_hi=pad([f32(r[1]) for r in rr], 0.0), nlev=L, B=B, n_lab=len(keep), C=Cn, P=P,
+              img=torch.tensor(offs + list(counts) + keep + compact, dtype=torch.int32), gts=_gapped(gts, GAP),
+              code_weight=list(par["code_weight"]), loss_weight=list(par["loss_weight"]),
+              **{k: par[k] for k in ("gamma", "alpha", "beta", "beta2d", "ctr_alpha", "dir_offset")})
+    maps = {}
+    for name, ch, scale in (("cls", Cn, 2.0), ("bbox", 13, 1.0), ("dir", 6, 1.0), ("ctr", 1, 1.0)):
+        maps[name] = [rnd(g, B, ch, h, w, scale=scale) for h, w in sizes]
+    # the assignment of this batch (the emulator's), to place values on positives and on background points
+    lab, tgt, cen = torch.zeros(len(keep), P, dtype=torch.int32), torch.zeros(len(keep), 13, P), torch.zeros(len(keep), P)
+    abi_emul.call("fcos3d_targets", **dict(kw, label=lab, target=tgt, centerness=cen))
+    lo = 0
+    for l, (h, w) in enumerate(sizes):
+        for k, b in enumerate(keep):
+            pts = torch.arange(lo, lo + h * w)
+            pos = pts[lab[k, lo:lo + h * w] < Cn]
+            # bbox predictions near their targets, so that both smooth-L1 branches are populated: target + N(0, 1) * (0.2 .. 3 betas)
+            bb = maps["bbox"][l][b].view(13, h * w)
+            bvec = torch.tensor([par["beta"]] * 9 + [par["beta2d"]] * 4)[:, None]
+            spread = 0.2 + 2.8 * torch.rand(13, pos.numel(), generator=g)
+            bb[:, pos - lo] = tgt[k][:, pos] + torch.randn(13, pos.numel(), generator=g) * spread * bvec
+            if pos.numel() >= 4:                                            # exactly the target on some positives: the df == 0 arm
+                bb[:, pos[::4] - lo] = tgt[k][:, pos[::4]]
+            if extreme:
+                cl, ct, dr = maps["cls"][l][b].view(Cn, h * w), maps["ctr"][l][b].view(1, h * w), maps["dir"][l][b].view(6, h * w)
+                vals = torch.tensor([30.0, -30.0, 90.0, -90.0])
+                for sel in (pos, pts[lab[k, lo:lo + h * w] >= Cn]):          # saturated logits at positive and at background points
+                    sel = sel[1::3] - lo
+                    cl[:, sel] = vals[torch.randint(0, 4, (Cn, sel.numel()), generator=g)]
+                    ct[0, sel] = vals[torch.randint(0, 4, (sel.numel(),), generator=g)]
+                far = pos[2::5] - lo                                        # direction logit pairs 100 apart, either way
+                dr[0::2, far] = dr[1::2, far] + 100.0 * (torch.randint(0, 2, (3, far.numel()), generator=g) * 2 - 1).float()
+        lo += h * w
+    for name in maps:
+        kw[name] = [_gapped(m, GAP) for m in maps[name]]
+    return kw, (lab, tgt, cen)
+
+
+def _fcos3d_outputs(kw):
+    n, P = kw["n_lab"], kw["P"]
+    return dict(label=_gapped(torch.full((n, P), 77, dtype=torch.int32), 77), target=_gapped(torch.full((n, 13, P), 7.0), 7.0),
+                centerness=_gapped(torch.full((n, P), 7.0), 7.0))
+
+
+def fcos3d_cases():
+    """fcos3d_targets / fcos3d_loss_fwd / fcos3d_loss_bwd at the smallest shapes that reach each path (FCOS3D_GEOMETRIES), the compact
+    image table with unlabelled first and last images, labelled images without gts (one, and all of them: num_pos == 0), 128 / 129 / 257
+    gts per image, the cs and alt parameter sets, gamma 1, 1 and 10 classes, saturated logits, predictions equal to their targets,
+    rotations on the direction bins' edges; the backward under distinct, one-hot and all-zero upstream gradients.  Outputs and the
+    prediction maps are views into larger storages (sentinels / 1e30 around them); the workspace is sized by the library and NaN-filled
+    in run_case.  The backward reads label / target / centerness / stats of the emulator's forward."""
+    cases = []
+    g = torch.Generator().manual_seed(97)
+    for tag, geom, par, counts, B, unl, C, _, sat in FCOS3D_BATCHES:
+        kw, _ = _fcos3d_case(g, geom, par, counts, B=B, unlabelled=unl, C=C, extreme=sat)
+        if tag in ("p286_alt_b4", "tiny_alt_gts128_129_257", "p286_alt_one_empty"):
+            tk = {k: v for k, v in kw.items() if k not in ("cls", "bbox", "dir", "ctr")}
+            cases.append((f"fcos3d_targets_{tag}", "fcos3d_targets", dict(tk, **_fcos3d_outputs(kw)), TOL_ROW))
+        fkw = dict(kw, **_fcos3d_outputs(kw), out=_gapped(torch.full((9,), 7.0), 7.0), stats=_gapped(torch.full((2,), 7.0), 7.0))
+        cases.append((f"fcos3d_loss_fwd_{tag}", "fcos3d_loss_fwd", fkw, TOL_ROW))
+        # the backward reads what the forward stored: the emulator's, on plain buffers
+        n, P = kw["n_lab"], kw["P"]
+        st = dict(label=torch.zeros(n, P, dtype=torch.int32), target=torch.zeros(n, 13, P), centerness=torch.zeros(n, P), out=torch.zeros(9),
+                  stats=torch.zeros(2))
+        abi_emul.call("fcos3d_loss_fwd", **dict(kw, **st))
+        gouts = [("w9", torch.tensor(FCOS3D_GOUT))]
+        if tag == "p286_alt_b4":
+            gouts += [(f"e{i}", torch.eye(9)[i].clone()) for i in range(9)] + [("zero", torch.zeros(9))]
+        for gtag, gout in gouts:
+            grads = {"d" + name: [_gapped(torch.full(m.shape, 7.0), 7.0) for m in kw[name]] for name in ("cls", "bbox", "dir", "ctr")}
+            bkw = dict(kw, label=_gapped(st["label"], 77), target=_gapped(st["target"], GAP), centerness=_gapped(st["centerness"], GAP),
+                       stats=_gapped(st["stats"], GAP), gout=_gapped(gout, GAP), **grads)
+            cases.append((f"fcos3d_loss_bwd_{tag}_{gtag}", "fcos3d_loss_bwd", bkw, TOL_ROW))
+    return cases
+
+
 # entry points the parity cases above do not run, and the test that checks each of them on the device instead
 COVERED_ELSEWHERE = {
     "adam_step": "tests/test_gpu_optim.py::test_adam_step_case",
     "grad_sqnorm": "tests/test_gpu_optim.py::test_grad_sqnorm_case",
     "segcopy": "tests/test_gpu_ops.py::test_segcopy_packs_refresh_and_gradient_scatter_on_device",
-    "fcos3d_targets": "tests/test_gpu_fcos3d.py::test_targets_match_the_reference_fixture",
-    "fcos3d_loss_fwd": "tests/test_gpu_fcos3d.py::test_losses_and_gradients_match_the_reference_fixture",
-    "fcos3d_loss_bwd": "tests/test_gpu_fcos3d.py::test_losses_and_gradients_match_the_reference_fixture",
 }
 
 
 def all_cases():
-    return gemm_cases() + attn_cases() + row_cases() + invpt_cases() + upconv_cases() + swin_cases() + loss_cases() + det_cases() + iou3d_cases() + product_config_cases()
+    return (gemm_cases() + attn_cases() + row_cases() + invpt_cases() + upconv_cases() + swin_cases() + loss_cases() + det_cases() + iou3d_cases() +
+            product_config_cases() + fcos3d_cases())

@@ -44,6 +44,7 @@ WORKSPACE_ARGS = {
     "colsum_batched": {"args[9]"}, "detloss_fwd": {"ws"}, "attn_msg_bwd": {"xargs[5]"}, "chanattn_bwd": {"xargs[5]"},
     "loss_label_stats": {"ws"}, "loss_fwd": {"ws"}, "nms_bev": {"args[6]"},
     "groupnorm_fwd": {"ws"}, "groupnorm_bwd": {"ws"}, "dcn_col2im_bwd": {"ws"}, "fcos_bbox_post_bwd": {"ws"},
+    "fcos3d_targets": {"ws"}, "fcos3d_loss_fwd": {"ws"}, "fcos3d_loss_bwd": {"ws"},       # (the assignment and the backward take a ws and do not use it)
 }
 
 # enum-like descriptor fields (0 = absent) and the enum-like positions of the positional entry points
@@ -373,6 +374,9 @@ def _model_leg(family, name, prec, mode, pitch32=None, drop=False):
 DET_LEVELS = ((32, 12, 20), (48, 6, 10), (64, 3, 5), (64, 3, 5))      # the level maps of tests/test_gpu_det_head.py
 
 
+DET_GTS, DET_LABEL_SEED = 8, 3
+
+
 def _det_leg(prec, mode):
     import det_ref
     head = mtt_amd.det_head.FCOS3DHead(**det_ref.mini_head_params())
@@ -380,6 +384,23 @@ def _det_leg(prec, mode):
     head.set_prec(prec)
     g = torch.Generator().manual_seed(5)
     feats = [torch.randn(2, c, h, w, generator=g) for c, h, w in DET_LEVELS]
+    # the train legs run the real criterion on the head's outputs (cs parameters, the strides of img_ds_ratio 0.75: a 128 x 213 image over
+    # the 12 x 20 level); image 1 is unlabelled, DET_LABEL_SEED gives num_pos > 20 (tests/test_replay_host.py asserts it)
+    dm = mtt_amd.det_model
+    crit = dm.configure_3ddet({"IMAGE_ORI_SIZE": (1024, 2048), "TRAIN": {"SCALE": (1024, 2048)}, "img_ds_ratio": 0.75})["detmodel"]
+    labels = dm.synthetic_det_labels(2, (128, 213), DET_GTS, unlabelled=(1,), seed=DET_LABEL_SEED)
+    # synthetic_det_labels draws boxes below level 0's range end, so every positive would sit on level 0 and the head's backward would see
+    # all-zero gradients on the other levels (whose kernels run first, and the recorder keeps the first call of a signature).  One more gt
+    # per higher level, a box around the image centre whose half size is 8 px past the level's range start, puts positives on every level
+    e, c = labels["det_labels"][0], torch.tensor([106.0, 64.0])
+    half = torch.tensor([[float(r[0]) + 8.0] for r in crit.regress_ranges[1:]])
+    n = half.shape[0]
+    e["bbox_modal"] = torch.cat([e["bbox_modal"], torch.cat([c - half, c + half], 1)])
+    e["center_I"] = torch.cat([e["center_I"], torch.cat([c.expand(n, 2), torch.full((n, 1), 20.0)], 1)])
+    e["label"] = torch.cat([e["label"], torch.arange(n) % crit.num_classes])
+    for k in ("center_S", "size_S", "rotation_S"):
+        e[k] = torch.cat([e[k], e[k][:n] * 0.5 + 0.25])
+    labels["det_label_number"][0] += n
 
     def run(_):
         if mode == "eval":
@@ -387,7 +408,9 @@ def _det_leg(prec, mode):
             with torch.no_grad():
                 head(feats)
         else:
-            sum(o.square().mean() for lst in head(feats) for o in lst).backward()
+            maps = [m.contiguous() for lst in head(feats) for m in lst]
+            sizes = [tuple(m.shape[-2:]) for m in maps[:len(maps) // 4]]
+            dm._DetLossFn.apply(crit, crit.pack_labels(labels, "cpu"), crit._geometry(sizes), *maps)[8].backward()
     return record(run)
 
 

@@ -437,3 +437,70 @@ def test_bbox_tail_fwd_bwd_vs_torch():
             assert _close(dsc, s.grad)
         else:
             assert float((dsc - 9.0).abs().max()) == 0.0
+
+
+# ---- ABI 15: the FCOS3D criterion emulators against both reference fixtures, through the product's own host wiring ---------------------
+def _fcos3d_fixture(stem):
+    import json
+    import os
+    import numpy as np
+    import conftest
+    with open(os.path.join(conftest.GOLDEN, stem + ".json")) as f:
+        meta = json.load(f)
+    return meta, np.load(os.path.join(conftest.GOLDEN, stem + ".npz"))
+
+
+def _fcos3d_elem_ok(g, ref):
+    """gpu_cases.compare's per-element rule at TOL_ROW: |g - ref| <= 1e-4 * rms(ref) + 4 fp32 ulps of ref"""
+    import gpu_cases
+    r, _ = gpu_cases._elem_ratio(g.double().reshape(-1), ref.double().reshape(-1), 10 * gpu_cases.TOL_ROW["f32"], False)
+    return float(r.max()) if r.numel() else 0.0
+
+
+FCOS3D_FIXTURE_CASES = [("fcos3d", "a"), ("fcos3d", "b"), ("fcos3d_alt", "a"), ("fcos3d_alt", "b")]
+
+
+@__import__("pytest").mark.parametrize("stem,name", FCOS3D_FIXTURE_CASES)
+def test_fcos3d_emulators_match_the_reference_fixtures_through_the_host_wiring(stem, name, emulated):
+    """DetModel.get_targets and _DetLossFn (its _desc, _geometry and pack_det_labels) with ops.call routed to the emulator, against the
+    unmodified reference's recorded values: labels exact, targets / centerness on positives 1e-6 relative, components and loss_sum 1e-5
+    relative, every gradient element within 1e-4 * rms + 4 fp32 ulps (the fixtures hold the reference's fp32 values: 2.8e-6 rms from
+    fp64 on case a).  Not through DetModel.loss: it refuses CPU tensors."""
+    import json
+    import numpy as np
+    import mtt_amd
+    from tests.golden import make_fcos3d_golden as mfg
+    dm = mtt_amd.det_model
+    meta, arrs = _fcos3d_fixture(stem)
+    c = meta["cases"][name]
+    C, L, sizes = meta["params"]["num_classes"], len(c["levels"]), [tuple(l) for l in c["levels"]]
+    crit = dm.DetModel(**json.loads(json.dumps(meta["params"])))
+    labels = mfg.load_labels(arrs, name, c["B"])
+    keep = [i for i in range(c["B"]) if int(labels["det_label_number"][i]) != 0]
+    dl = [labels["det_labels"][i] for i in keep]
+    lab, tgt, ctr = crit.get_targets(crit.get_points(sizes, torch.float32, "cpu"), [e["bbox_modal"] for e in dl], [e["label"] for e in dl],
+                                     [torch.cat([e["center_S"], e["size_S"], e["rotation_S"]], 1) for e in dl], [e["label"] for e in dl],
+                                     [e["center_I"][:, :2] for e in dl], [e["center_I"][:, 2] for e in dl])
+    lab, tgt, ctr = torch.cat(lab), torch.cat(tgt), torch.cat(ctr)
+    assert torch.equal(lab, torch.from_numpy(arrs[f"{name}/labels"].astype(np.int64)))
+    pos = lab < C
+    assert int(pos.sum()) == c["num_pos"]
+    rt, rc = torch.from_numpy(arrs[f"{name}/pos_targets"]), torch.from_numpy(arrs[f"{name}/pos_ctr"])
+    worst = lambda a, r: float(((a - r).abs() / r.abs().clamp(min=1e-6)).max()) if r.numel() else 0.0
+    assert worst(tgt[pos], rt) <= 1e-6 and worst(ctr[pos], rc) <= 1e-6
+
+    flat = [torch.from_numpy(arrs[f"{name}/pred{j}"]).requires_grad_(True) for j in range(4 * L)]
+    out = dm._DetLossFn.apply(crit, crit.pack_labels(labels, "cpu"), crit._geometry(sizes), *flat)
+    for i, k in enumerate(dm.LOSS_KEYS):
+        ref = c["loss"][k]
+        assert (float(out[i]) == 0.0) if ref == 0.0 else abs(float(out[i]) - ref) <= 1e-5 * abs(ref), (k, float(out[i]), ref)
+    assert abs(float(out[8]) - c["loss_sum"]) <= 1e-5 * abs(c["loss_sum"])
+    gout = torch.tensor(meta["gout"]) if "gout" in meta else torch.tensor([0.0] * 8 + [1.0])
+    grads = torch.autograd.grad((out * gout).sum(), flat, retain_graph=True)
+    for j, g in enumerate(grads):
+        ref = torch.from_numpy(arrs[f"{name}/grad{j}"])
+        assert _fcos3d_elem_ok(g, ref) <= 1.0, (j, _fcos3d_elem_ok(g, ref))
+    if stem == "fcos3d" and name == "a":                                     # one component alone: gout = e4
+        grads = torch.autograd.grad(out[4], flat)
+        for j, g in enumerate(grads):
+            assert _fcos3d_elem_ok(g, torch.from_numpy(arrs[f"a/grad_rotsin{j}"])) <= 1.0, j

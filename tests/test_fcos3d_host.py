@@ -176,3 +176,69 @@ def test_fused_multitask_loss_takes_the_criterion_from_p():
     crit = mtt_amd.losses.FusedMultiTaskLoss(p, ['semseg', 'depth', '3ddet'], {'semseg': 100.0, 'depth': 1.0, '3ddet': 1.0})
     assert crit.detmodel is p.detmodel and set(crit.spec) == {'semseg', 'depth'}
     assert mtt_amd.losses.FusedMultiTaskLoss(p, ['semseg', '3ddet']).loss_weights == {'semseg': 1.0, '3ddet': 1.0}
+
+
+# ---- the alt parameter set (tests/golden/fcos3d_alt.*): nothing coincides ----------------------------------------------------------------
+def _alt_fixture():
+    with open(os.path.join(conftest.GOLDEN, "fcos3d_alt.json")) as f:
+        meta = json.load(f)
+    return meta, np.load(os.path.join(conftest.GOLDEN, "fcos3d_alt.npz"))
+
+
+def test_reference_regenerates_the_alt_fixture(tmp_path):
+    """as test_reference_regenerates_the_fixture, for tests/golden/fcos3d_alt.*"""
+    import subprocess
+    import sys
+    if not os.path.isdir(os.path.join(mfg.REF, "TaskPrompter", "detection_toolbox")):
+        pytest.skip("reference tree not present")
+    r = subprocess.run([sys.executable, mfg.__file__, str(tmp_path), "alt"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    size = 0
+    for name in ("fcos3d_alt.json", "fcos3d_alt.npz"):
+        assert open(tmp_path / name, "rb").read() == open(os.path.join(conftest.GOLDEN, name), "rb").read(), name
+        size += os.path.getsize(os.path.join(conftest.GOLDEN, name))
+    assert size < 512 * 1024
+
+
+def test_alt_parameter_set_has_no_coincidences():
+    meta, arrs = _alt_fixture()
+    p = meta["params"]
+    lw = [p[k]["loss_weight"] for k in ("loss_cls", "loss_bbox", "loss_dir", "loss_centerness", "loss_bbox2d")]
+    assert len(set(lw)) == 5 and len(set(p["code_weight"])) == 13 and len(set(meta["gout"])) == 9 and all(meta["gout"])
+    assert p["loss_cls"]["gamma"] not in (2.0,) and p["loss_cls"]["gamma"] >= 1 and p["loss_cls"]["alpha"] != 0.25
+    assert p["loss_bbox"]["beta"] != p["loss_bbox2d"]["beta"] and p["dir_offset"] != 0 and p["centerness_alpha"] != 2.5
+    assert p["center_sample_radius"] != 1.5 and p["num_classes"] != 6
+    a, b = meta["cases"]["a"], meta["cases"]["b"]
+    assert a["num_pos"] > 20 and b["num_pos"] == 0 and int(arrs["a/num"][1]) == 0
+    assert int(arrs["a/labels"].max()) == p["num_classes"] and set(np.unique(arrs["a/labels"])) == set(range(p["num_classes"] + 1))
+
+
+@pytest.mark.parametrize("name", ["a", "b"])
+def test_restatement_reproduces_the_alt_fixture(name):
+    """tests/fcos3d_ref.py under the alt set, at the bounds of test_restatement_reproduces_the_reference_fixture; the gradient is the
+    fixture's one weighted set, d (sum_i w_i * component_i + w_8 * loss_sum)"""
+    meta, arrs = _alt_fixture()
+    C = meta["params"]["num_classes"]
+    c, labels, preds = _case(meta, arrs, name)
+    sizes = [tuple(l) for l in c["levels"]]
+    keep, lab, tgt, cen = fcos3d_ref.assign(meta["params"], labels, sizes)
+    lab_r = _ref_layout(lab, sizes)
+    assert np.array_equal(lab_r.numpy(), arrs[f"{name}/labels"].astype(np.int64))
+    pos = lab_r < C
+    assert int(pos.sum()) == c["num_pos"]
+    assert torch.equal(_ref_layout(tgt, sizes)[pos], torch.from_numpy(arrs[f"{name}/pos_targets"]))
+    assert np.allclose(_ref_layout(cen, sizes)[pos].numpy(), arrs[f"{name}/pos_ctr"], rtol=1e-6, atol=0)
+    leaves = [[p.clone().requires_grad_(True) for p in lst] for lst in preds]
+    ld, ls = fcos3d_ref.loss(meta["params"], leaves, labels)
+    assert sorted(ld) == sorted(c["loss"])
+    for k, v in ld.items():
+        assert abs(float(v) - c["loss"][k]) <= 1e-6 * max(abs(c["loss"][k]), 1e-6), (k, float(v), c["loss"][k])
+    assert abs(float(ls) - c["loss_sum"]) <= 1e-6 * max(abs(c["loss_sum"]), 1e-6)
+    w = meta["gout"]
+    total = sum(w[i] * ld[k] for i, k in enumerate(fcos3d_ref.KEYS)) + w[8] * ls
+    flat = [p for lst in leaves for p in lst]
+    grads = torch.autograd.grad(total, flat, allow_unused=True)
+    for j, (p, g) in enumerate(zip(flat, grads)):
+        ref = torch.from_numpy(arrs[f"{name}/grad{j}"]).double()
+        g = torch.zeros_like(ref) if g is None else g.double()
+        assert float((g - ref).abs().max()) <= 1e-6 * max(float(ref.abs().max()), 1e-30), j

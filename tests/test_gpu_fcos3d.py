@@ -291,3 +291,126 @@ def test_fused_multitask_loss_with_3ddet():
     assert _rel(float(out['total']), want) < 1e-6
     ld, ls = p["detmodel"].loss(preds, labels)
     assert float(out['3ddet']) == float(ls)
+
+
+# ---- every component on its own, under the cs and the alt parameter set and on a batch without gts ------------------------------------------
+def _alt_fixture():
+    with open(os.path.join(conftest.GOLDEN, "fcos3d_alt.json")) as f:
+        meta = json.load(f)
+    return meta, np.load(os.path.join(conftest.GOLDEN, "fcos3d_alt.npz"))
+
+
+def _forward(crit, labels, maps, call):
+    """fcos3d_loss_fwd as _DetLossFn.forward launches it, through `call` (the device's ops.call or the emulator) -> (out [9], stats [2])"""
+    import mtt_amd
+    dev = maps[0].device
+    L = len(maps) // 4
+    packed = crit.pack_labels(labels, dev)
+    geo = crit._geometry([tuple(m.shape[-2:]) for m in maps[:L]])
+    P, n = geo["P"], packed.n_lab
+    label = torch.full((n, P), -7, dtype=torch.int32, device=dev)
+    target, ctr = torch.full((n, 13, P), 7.0, device=dev), torch.full((n, P), 7.0, device=dev)
+    out, stats = torch.full((9,), 7.0, device=dev), torch.full((2,), 7.0, device=dev)
+    kw = crit._desc(geo, packed, label, target, ctr)
+    kw.update(cls=list(maps[:L]), bbox=list(maps[L:2 * L]), dir=list(maps[2 * L:3 * L]), ctr=list(maps[3 * L:]), out=out, stats=stats)
+    if dev.type == "cuda":
+        kw["ws"] = mtt_amd.ops.ws_for("fcos3d", dev, P=P, n_lab=n)
+    call("fcos3d_loss_fwd", **kw)
+    return out.cpu(), stats.cpu()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["cs", "alt", "zero_gt"])
+def test_each_component_matches_its_reference(which):
+    """out[9] spans a factor of 60 between loss_cls and loss_offset, so compare's rms-relative element bound is loose for the small
+    components: each of the nine values within 1e-5 relative (the existing component bound, about 150 x the fp32 reference's own 6e-8
+    distance from fp64) of the reference fixture (cs: fcos3d.* a; alt: fcos3d_alt.* a), or of the fp64 emulator on a batch whose labelled
+    images have no gts (the reference cannot run those); exact zeros exactly zero; stats exact."""
+    _need_gpu()
+    import mtt_amd
+    from oracle import abi_emul
+    if which == "zero_gt":
+        meta, _ = _alt_fixture()
+        crit = _crit(meta)
+        levels = ((10, 20), (5, 10), (3, 5), (3, 5), (2, 3))
+        labels = mtt_amd.det_model.synthetic_det_labels(3, (110, 215), [0, 4, 0], num_classes=3, unlabelled=(1,), seed=2)
+        g = torch.Generator().manual_seed(21)
+        maps = [torch.randn(3, ch, h, w, generator=g) * (2.0 if k == 0 else 1.0) for k, ch in enumerate((3, 13, 6, 1)) for h, w in levels]
+        ref, rstats = _forward(crit, labels, maps, abi_emul.call)
+        ref, num_pos, n_lab = ref.double().tolist(), 0, 2
+        assert rstats.tolist() == [0.0, 2.0] and ref[0] > 0 and not any(ref[1:8])
+    else:
+        meta, arrs = _fixture() if which == "cs" else _alt_fixture()
+        c = meta["cases"]["a"]
+        crit = _crit(meta)
+        labels = mfg.load_labels(arrs, "a", c["B"])
+        maps = [torch.from_numpy(arrs[f"a/pred{j}"]) for j in range(4 * len(c["levels"]))]
+        ref = [c["loss"][k] for k in fcos3d_ref.KEYS] + [c["loss_sum"]]
+        num_pos, n_lab = c["num_pos"], 2
+    out, stats = _forward(crit, labels, [m.to(DEV) for m in maps], mtt_amd.ops.call)
+    for i, r in enumerate(ref):
+        got = float(out[i])
+        print(f"{which} out[{i}]: device {got!r} reference {r!r} rel {_rel(got, r) if r else 0.0:.2e}")
+    for i, r in enumerate(ref):
+        got = float(out[i])
+        assert (got == 0.0) if r == 0.0 else _rel(got, r) <= 1e-5, (i, got, r)
+    assert stats.tolist() == [float(num_pos), float(num_pos + n_lab)]
+
+
+@pytest.mark.gpu
+def test_alt_weighted_gradient_matches_the_reference_per_element():
+    """d (sum_i w_i * component_i + w_8 * loss_sum) / d every map under the alt set, nine distinct w: every element within
+    1e-4 * rms(reference map) + 4 fp32 ulps (gpu_cases.compare's rule at TOL_ROW) of the unmodified reference's gradient"""
+    _need_gpu()
+    import mtt_amd
+    import gpu_cases
+    meta, arrs = _alt_fixture()
+    c = meta["cases"]["a"]
+    L = len(c["levels"])
+    crit = _crit(meta)
+    flat, preds = _preds(arrs, "a", L)
+    ld, ls = crit.loss(preds, mfg.load_labels(arrs, "a", c["B"]))
+    w = meta["gout"]
+    total = sum(w[i] * ld[k] for i, k in enumerate(fcos3d_ref.KEYS)) + w[8] * ls
+    grads = torch.autograd.grad(total, flat)
+    worst = 0.0
+    for j, g in enumerate(grads):
+        ref = torch.from_numpy(arrs[f"a/grad{j}"]).double().reshape(-1)
+        r, _ = gpu_cases._elem_ratio(g.cpu().double().reshape(-1), ref, 10 * gpu_cases.TOL_ROW["f32"], False)
+        worst = max(worst, float(r.max()))
+        assert float(r.max()) <= 1.0, (j, float(r.max()))
+        assert not g[1].any(), "the unlabelled image must get zero gradient"
+    print(f"alt weighted gradient: worst element error / bound {worst:.3e}")
+
+
+def _parity_forward_cases():
+    import gpu_cases
+    return [f"fcos3d_loss_fwd_{b[0]}" for b in gpu_cases.FCOS3D_BATCHES if not b[8]]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", _parity_forward_cases())
+def test_parity_case_components_match_the_emulator_individually(name):
+    """the forward parity cases of gpu_cases.fcos3d_cases() without saturated logits (gamma 1, 1 and 10 classes, one and eight levels,
+    images without gts, 128 / 129 / 257 gts): compare's element bound on `out` is relative to the rms of all nine values, which loss_cls
+    dominates, so here each component is held to 1e-5 relative of the fp64 emulator (the component bound of the tests above), exact zeros
+    exactly zero, stats exact"""
+    _need_gpu()
+    import gpu_cases
+    import mtt_amd
+    from oracle import abi_emul
+    kw = next(c[2] for c in gpu_cases.fcos3d_cases() if c[0] == name)
+    ekw, _ = gpu_cases.clone_storages(kw)
+    abi_emul.call("fcos3d_loss_fwd", **ekw)
+    dev = lambda v: v.to(DEV).contiguous() if isinstance(v, torch.Tensor) else v
+    gkw = {k: [dev(a) for a in v] if isinstance(v, (list, tuple)) else dev(v) for k, v in kw.items()}
+    gkw["ws"] = mtt_amd.ops.ws_for("fcos3d", torch.device(DEV), P=kw["P"], n_lab=kw["n_lab"])
+    mtt_amd.ops.call("fcos3d_loss_fwd", **gkw)
+    out, ref = gkw["out"].cpu().double(), ekw["out"].double()
+    for i in range(9):
+        got, r = float(out[i]), float(ref[i])
+        print(f"{name} out[{i}]: device {got!r} emulator {r!r} rel {_rel(got, r) if r else 0.0:.2e}")
+    for i in range(9):
+        got, r = float(out[i]), float(ref[i])
+        assert (got == 0.0) if r == 0.0 else _rel(got, r) <= 1e-5, (i, got, r)
+    assert torch.equal(gkw["stats"].cpu(), ekw["stats"])

@@ -85,6 +85,35 @@ def test_exclusion_list_is_closed():
     assert set(ru.NOT_REPLAYABLE) <= set(gpu_cases.COVERED_ELSEWHERE)
 
 
+@pytest.mark.parametrize("prec", ["x3f", "bf16"])
+def test_det_train_leg_launches_the_real_criterion(prec):
+    """the 3ddet train legs run _DetLossFn on the head's outputs: fcos3d_loss_fwd and fcos3d_loss_bwd are recorded once each, with one
+    image unlabelled and more than 20 positive points"""
+    rec = ru.record_leg(f"det_head-mini-{prec}-train")
+    assert rec.entries["fcos3d_loss_fwd"] == 1 and rec.entries["fcos3d_loss_bwd"] == 1
+    fwd = next(s for s in rec.snaps if s.entry == "fcos3d_loss_fwd")
+    kw, _ = fwd.fresh()
+    assert kw["B"] == 2 and kw["n_lab"] == 1
+    abi_emul.call("fcos3d_loss_fwd", **kw)
+    assert float(kw["stats"][0]) > 20, float(kw["stats"][0])
+    assert "fcos3d_loss_fwd" not in ru.record_leg(f"det_head-mini-{prec}-eval").entries
+    # positives on every level, so that the first (kept) call of every backward signature carries a gradient: no snapshot of the leg writes
+    # only zeros, and none reads an all-zero gradient
+    lab = kw["label"].view(-1)
+    lo = 0
+    for l in range(kw["nlev"]):
+        n = kw["H"][l] * kw["W"][l]
+        assert int((lab[lo:lo + n] < kw["C"]).sum()) > 0, f"no positive on level {l}"
+        lo += n
+    for s in rec.snaps:
+        assert s.wrote and all(bool(v.double().abs().max() > 0) for v in s.wrote.values() if v.numel()), f"{s.entry} at {s.site} writes only zeros"
+        if s.entry.endswith("_bwd"):
+            skw, _ = s.fresh()
+            for name in ("dy", "dout", "dcol", "gout"):
+                if isinstance(skw.get(name), torch.Tensor):
+                    assert bool(skw[name].double().abs().max() > 0), f"{s.entry} at {s.site}: {name} is all zero"
+
+
 def test_workspace_table_covers_the_scratch_arguments_of_the_cases():
     for cname, entry, kw, _ in tpc.CASES:
         for lbl, t in gpu_cases._arg_tensors(kw):
