@@ -906,6 +906,56 @@ size_t mtt_cs3d_desc_size(void);
 int mtt_cs3d_image(const mtt_cs3d_desc* d, void* stream);
 int mtt_cs3d_labels(const mtt_cs3d_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Rendering predictions on the device (additive exports, ABI 17 unchanged): what the reference's vis_pred_for_one_task
+ * (TaskPrompter/utils/visualization_utils.py:122-198) and save_model_pred_for_one_task (evaluation/evaluate_utils.py:126-154) do to a
+ * prediction before it is encoded into a file, in one pass over the logits.  Both entry points launch on the caller's stream, never
+ * synchronise and return MTT_E_* without launching anything when the descriptor is refused.
+ *
+ * src fp32 NCHW [B, C, h, w], read in place.  Per pixel (y, x) of the (H, W) grid, all in fp32 registers:
+ *   1. bilinear interpolation with align_corners = False under PyTorch's rules: scale = (float)in / out, source coordinate
+ *      s = max(scale * (d + 0.5) - 0.5, 0), lower tap i0 = min((int)s, in - 1), upper tap min(i0 + 1, in - 1), weights 1 - l and l with
+ *      l = s - i0; the horizontal pair of each row first, (1 - lx) * v0 + lx * v1, then the vertical one, no fused multiply-adds.
+ *      (H, W) == (h, w) takes a path without taps and returns the source values themselves.
+ *   2. the rule of get_output (TaskPrompter/utils/utils.py:27-63) selected by `mode`:
+ *        MTT_RENDER_CLASS         arg-max over C (1..256), the first index wins ties
+ *        MTT_RENDER_SIGMOID255    C == 1: 255 / (1 + exp(-x))
+ *        MTT_RENDER_SOFTMAX1_255  C == 2: exp(x1 - m) / (exp(x0 - m) + exp(x1 - m)) * 255, m = max(x0, x1)
+ *        MTT_RENDER_NORMALS       C == 3: (x / max(sqrt(x0^2 + x1^2 + x2^2), 1e-12) + 1) * 255 / 2 per component
+ *        MTT_RENDER_DEPTH         C == 1: x > 0 ? x : 0
+ *   3. the output selected by `out_kind`:
+ *        MTT_RENDER_OUT_U8        uint8 [.., H, W]: the class index; the value truncated (SIGMOID255, SOFTMAX1_255); for DEPTH the index
+ *                                 (v - min_b) / (max_b - min_b) * 255 truncated, min_b / max_b read from `minmax` (mtt_render_minmax), and 0
+ *                                 everywhere when max_b == min_b (the reference divides 0 by 0 there)
+ *        MTT_RENDER_OUT_LUT1      uint8 [.., H, W]: table[index], table uint8 [256] on the device (CLASS only)
+ *        MTT_RENDER_OUT_LUT3      uint8 [.., H, W, 3]: table[index][0..2], table uint8 [256, 3] on the device, in the table's channel
+ *                                 order (CLASS, DEPTH)
+ *        MTT_RENDER_OUT_RGB3      uint8 [.., H, W, 3]: the three truncated components, reversed when swap_rb != 0 (NORMALS only)
+ *        MTT_RENDER_OUT_F32       fp32 [.., H, W] (DEPTH only)
+ *   4. the window: win == NULL writes the whole grid, image b at pixel offset b * H * W.  Otherwise win is int64 [B, 5] on the device,
+ *      rows (y0, x0, H_out, W_out, offset): image b writes the pixels [y0, y0 + H_out) x [x0, x0 + W_out) of its grid, packed, starting
+ *      at pixel `offset` of out.  win_host is the host copy, which the entry point validates: windows inside the grid, offsets
+ *      non-negative, offset + H_out * W_out <= out_pixels (the capacity of out in pixels, checked without a window too).
+ * Four pixels per thread along x (16-byte loads at equal size, one 4-, 12- or 16-byte store) when w, W, every window's x0, W_out and
+ * offset are multiples of 4 and src / out are 16-byte aligned; otherwise one pixel per thread, any size and alignment.
+ *
+ * mtt_render_minmax  C == 1: per-image minimum and maximum of the interpolated, clamped map over the same pixels, as unsigned integer
+ *   atomics on the bit patterns of the non-negative floats (exact, independent of order).  minmax uint32 [2, B]: row 0 the minima, row 1
+ *   the maxima; the entry point initialises both before the launch. */
+enum { MTT_RENDER_CLASS = 0, MTT_RENDER_SIGMOID255 = 1, MTT_RENDER_SOFTMAX1_255 = 2, MTT_RENDER_NORMALS = 3, MTT_RENDER_DEPTH = 4 };
+enum { MTT_RENDER_OUT_U8 = 0, MTT_RENDER_OUT_LUT1 = 1, MTT_RENDER_OUT_LUT3 = 2, MTT_RENDER_OUT_RGB3 = 3, MTT_RENDER_OUT_F32 = 4 };
+typedef struct {
+  const float* src; void* out; const uint8_t* table;
+  const int64_t* win; const int64_t* win_host;
+  uint32_t* minmax;
+  int64_t out_pixels;
+  int32_t B, C, h, w, H, W;
+  int32_t mode, out_kind, swap_rb;
+} mtt_render_desc;
+size_t mtt_render_desc_size(void);
+int mtt_render_map(const mtt_render_desc* d, void* stream);
+int mtt_render_minmax(const mtt_render_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -260,6 +260,11 @@ class Cs3dDesc(C.Structure):
                 ("mean", f32 * 3), ("std", f32 * 3)]
 
 
+class RenderDesc(C.Structure):
+    _fields_ = [("src", ptr), ("out", ptr), ("table", ptr), ("win", ptr), ("win_host", ptr), ("minmax", ptr), ("out_pixels", i64),
+                ("B", i32), ("C", i32), ("h", i32), ("w", i32), ("H", i32), ("W", i32), ("mode", i32), ("out_kind", i32), ("swap_rb", i32)]
+
+
 # entry point -> (descriptor struct, size index in mtt_desc_size) ; None = positional-argument entry
 DESCS = {
     "loss_fwd": LossDesc,
@@ -345,11 +350,17 @@ E_BADARG, E_ALIGN, E_UNSUPPORTED = -1, -2, -3                                   
 CS3D = {"cs3d_image": Cs3dDesc, "cs3d_labels": Cs3dDesc}
 CS3D_TILE_H, CS3D_TILE_W, CS3D_MAX_ROWS, CS3D_MAX_COLS = 16, 64, 208, 5440         # MTT_CS3D_* of include/mtt_hip.h
 
+# Rendering predictions (csrc/render.hip): additive exports under ABI 17 as well, covered by tests/test_gpu_render.py.  win_host is the
+# host copy of the window table, a CPU tensor: `render_call` passes its address.
+RENDER = {"render_map": RenderDesc, "render_minmax": RenderDesc}
+RENDER_CLASS, RENDER_SIGMOID255, RENDER_SOFTMAX1_255, RENDER_NORMALS, RENDER_DEPTH = range(5)       # MTT_RENDER_* of include/mtt_hip.h
+RENDER_OUT_U8, RENDER_OUT_LUT1, RENDER_OUT_LUT3, RENDER_OUT_RGB3, RENDER_OUT_F32 = range(5)         # MTT_RENDER_OUT_*
+
 # workspace-size queries mtt_<entry>_ws_floats(const desc*) of the entry points whose cross-workgroup reductions go through caller-owned partials
 WS_QUERIES = {"gemm_colsum": GemmDesc, "chan_logits": ChanLogitDesc, "modulate_bwd": ModulateDesc, "ctr_dw": CtrDesc, "attn_msg_bwd": AttnMsgDesc, "loss": LossDesc,
               "chanattn_bwd": ChanAttnDesc, "detloss": DetLossDesc,
               "groupnorm": GnDesc, "dcn_col2im": DcnDesc, "fcos_bbox_post": BboxPostDesc, "fcos3d": Fcos3dDesc}
-EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_fcos3d_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes", "mtt_det_decode_desc_size", "mtt_det_nms_ws_bytes", "mtt_eval_desc_size", "mtt_eval_ws_floats"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA) + list(POSTPROC) + list(EVAL)] + ["mtt_aug_desc_size"] + ["mtt_" + n for n in AUGMENT] + ["mtt_cs3d_desc_size"] + ["mtt_" + n for n in CS3D]
+EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_fcos3d_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes", "mtt_det_decode_desc_size", "mtt_det_nms_ws_bytes", "mtt_eval_desc_size", "mtt_eval_ws_floats"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA) + list(POSTPROC) + list(EVAL)] + ["mtt_aug_desc_size"] + ["mtt_" + n for n in AUGMENT] + ["mtt_cs3d_desc_size"] + ["mtt_" + n for n in CS3D] + ["mtt_render_desc_size"] + ["mtt_" + n for n in RENDER]
 
 _lib = None
 
@@ -407,7 +418,12 @@ def load():
     lib.mtt_cs3d_desc_size.argtypes = []
     if lib.mtt_cs3d_desc_size() != C.sizeof(Cs3dDesc):
         raise RuntimeError(f"descriptor layout mismatch for Cs3dDesc: C {lib.mtt_cs3d_desc_size()} vs ctypes {C.sizeof(Cs3dDesc)}")
-    for name, st in list(DESCS.items()) + list(POSTPROC.items()) + list(EVAL.items()) + list(AUGMENT.items()) + list(CS3D.items()):
+    lib.mtt_render_desc_size.restype = C.c_size_t
+    lib.mtt_render_desc_size.argtypes = []
+    if lib.mtt_render_desc_size() != C.sizeof(RenderDesc):
+        raise RuntimeError(f"descriptor layout mismatch for RenderDesc: C {lib.mtt_render_desc_size()} vs ctypes {C.sizeof(RenderDesc)}")
+    for name, st in (list(DESCS.items()) + list(POSTPROC.items()) + list(EVAL.items()) + list(AUGMENT.items()) + list(CS3D.items())
+                     + list(RENDER.items())):
         fn = getattr(lib, "mtt_" + name)
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(st), ptr]
@@ -494,6 +510,27 @@ def cs3d_call(name, stream=None, **fields):
             arr = getattr(desc, k)
             for i, e in enumerate(v):
                 arr[i] = e
+        elif v is not None:
+            setattr(desc, k, v)
+    rc = getattr(lib, "mtt_" + name)(C.byref(desc), _stream() if stream is None else stream)
+    if rc > 0:
+        raise RuntimeError(f"mtt_{name} failed with status {rc} (hipError_t)")
+    return rc
+
+
+def render_call(name, stream=None, **fields):
+    """mtt_<name> of RENDER.  Device tensors become device pointers (a CPU tensor raises); win_host takes a CPU tensor.  Returns 0 or a
+    negative MTT_E_* status (a refused descriptor, nothing launched); a hipError_t raises."""
+    lib = load()
+    desc = RenderDesc()
+    for k, v in fields.items():
+        if isinstance(v, torch.Tensor):
+            if k == "win_host":
+                if v.is_cuda:
+                    raise RuntimeError("win_host is the host copy of the window table and must be a CPU tensor")
+                setattr(desc, k, v.data_ptr())
+            else:
+                setattr(desc, k, _addr(v))
         elif v is not None:
             setattr(desc, k, v)
     rc = getattr(lib, "mtt_" + name)(C.byref(desc), _stream() if stream is None else stream)
