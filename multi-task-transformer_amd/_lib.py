@@ -4,6 +4,12 @@
 arguments — torch tensors (or views: only the base address is used) for pointer fields, ints /
 floats for the rest — launches it on torch's current HIP stream and raises on a non-zero status.
 
+Every export is declared once: the family tables (DESCS, POSITIONAL, DESC_EXTRA, POSTPROC, EVAL,
+AUGMENT, CS3D, RENDER, WS_QUERIES) and HELPERS make up SIGNATURES, symbol -> (restype, argtypes,
+descriptor struct), and `load()` sets every restype / argtypes from it in one loop, checks every
+descriptor size of SIZE_QUERIES in another, and nothing assigns a signature afterwards.  One
+function, `_fill`, turns keyword fields into a descriptor for every launcher and size query.
+
 There is NO fallback: if the shared library is missing or a tensor is not on a HIP device the
 call raises.  (tests/ may monkeypatch `call` with the CPU emulator in oracle/abi_emul.py to
 exercise the host-side wiring without a GPU; the product never does.)
@@ -100,6 +106,9 @@ class CtrDesc(C.Structure):
 class ResizeDesc(C.Structure):
     _fields_ = [("in_", ptr), ("out", ptr), ("B", i32), ("C", i32), ("Hin", i32), ("Win", i32), ("Hout", i32), ("Wout", i32),
                 ("ld_in", i64), ("ld_out", i64), ("in_dtype", i32), ("out_dtype", i32), ("out_nchw", i32), ("accumulate", i32)]
+
+
+setattr(ResizeDesc, "in", ResizeDesc.in_)        # `in` is a keyword: callers pass **{"in": t}, and it names the same field
 
 
 class BnDesc(C.Structure):
@@ -247,6 +256,7 @@ class EvalDesc(C.Structure):
 
 
 class AugDesc(C.Structure):
+    _host_ = ("table_host", "off_host")       # host copies the entry point validates: `_fill` takes CPU tensors for these fields
     _fields_ = [("src", ptr), ("off", ptr), ("off_host", ptr), ("table", ptr), ("table_host", ptr), ("out", ptr), ("flags", ptr),
                 ("src_numel", i64), ("cat_max_ratio", C.c_double),
                 ("B", i32), ("h", i32), ("w", i32), ("C", i32), ("src_u8", i32), ("kind", i32), ("photometric", i32), ("depth_ignore", i32),
@@ -254,6 +264,7 @@ class AugDesc(C.Structure):
 
 
 class Cs3dDesc(C.Structure):
+    _host_ = ("xtab_host", "ytab_host")
     _fields_ = [("src", ptr), ("disp", ptr), ("xtab", ptr), ("ytab", ptr), ("xtab_host", ptr), ("ytab_host", ptr), ("xcoeff", ptr), ("ycoeff", ptr),
                 ("out", ptr), ("semseg", ptr), ("flags", ptr),
                 ("B", i32), ("H", i32), ("W", i32), ("h", i32), ("w", i32), ("xn", i32), ("yn", i32), ("xk", i32), ("yk", i32), ("bgr", i32),
@@ -261,11 +272,12 @@ class Cs3dDesc(C.Structure):
 
 
 class RenderDesc(C.Structure):
+    _host_ = ("win_host",)
     _fields_ = [("src", ptr), ("out", ptr), ("table", ptr), ("win", ptr), ("win_host", ptr), ("minmax", ptr), ("out_pixels", i64),
                 ("B", i32), ("C", i32), ("h", i32), ("w", i32), ("H", i32), ("W", i32), ("mode", i32), ("out_kind", i32), ("swap_rb", i32)]
 
 
-# entry point -> (descriptor struct, size index in mtt_desc_size) ; None = positional-argument entry
+# descriptor entry points mtt_<name>(const desc*, stream): name -> descriptor struct
 DESCS = {
     "loss_fwd": LossDesc,
     "gemm": GemmDesc, "attn_fwd": AttnDesc, "softmax_fwd": SoftmaxDesc, "softmax_bwd": SoftmaxDesc,
@@ -282,10 +294,17 @@ DESCS = {
     "nearest_add": NearestDesc, "nearest_add_bwd": NearestDesc, "fcos_bbox_post": BboxPostDesc, "fcos_bbox_post_bwd": BboxPostDesc,
     "fcos3d_targets": Fcos3dDesc, "fcos3d_loss_fwd": Fcos3dDesc, "fcos3d_loss_bwd": Fcos3dDesc,
 }
-_SIZE_INDEX = [GemmDesc, AttnDesc, SoftmaxDesc, LnDesc, ChanLogitDesc, ModulateDesc, CtrDesc, ResizeDesc, BnDesc, ConvGeom,
-               DwconvDesc, PoolDesc, LnMtDesc, AttnMsgDesc, ConvtDesc, AdamDesc, LossDesc, UpconvDesc,
-               GatherDesc, WinAttnDesc, ChanAttnDesc, Conv3s2Desc, SegcopyDesc, CtrwDesc, DetLossDesc]
-_DET_SIZE_INDEX = [GnDesc, DcnDesc, NearestDesc, BboxPostDesc]        # mtt_det_desc_size (ABI 14)
+# every sizeof() the library reports, checked against the mirror by load(): (query symbol, index or None, struct)
+SIZE_QUERIES = [("mtt_desc_size", i, st) for i, st in enumerate([
+    GemmDesc, AttnDesc, SoftmaxDesc, LnDesc, ChanLogitDesc, ModulateDesc, CtrDesc, ResizeDesc, BnDesc, ConvGeom,
+    DwconvDesc, PoolDesc, LnMtDesc, AttnMsgDesc, ConvtDesc, AdamDesc, LossDesc, UpconvDesc,
+    GatherDesc, WinAttnDesc, ChanAttnDesc, Conv3s2Desc, SegcopyDesc, CtrwDesc, DetLossDesc])]
+SIZE_QUERIES += [("mtt_det_desc_size", i, st) for i, st in enumerate([GnDesc, DcnDesc, NearestDesc, BboxPostDesc])]       # ABI 14
+SIZE_QUERIES += [("mtt_fcos3d_desc_size", None, Fcos3dDesc), ("mtt_det_decode_desc_size", None, DetDecodeDesc),           # ABI 15, 16
+                 ("mtt_eval_desc_size", None, EvalDesc), ("mtt_aug_desc_size", None, AugDesc),                           # ABI 17
+                 ("mtt_cs3d_desc_size", None, Cs3dDesc), ("mtt_render_desc_size", None, RenderDesc)]
+
+# positional entry points mtt_<name>(args..., stream): name -> argtypes, the stream included
 POSITIONAL = {
     "patchify16": [ptr, ptr, C.c_int, C.c_int, C.c_int, C.c_int, ptr],
     "patchify": [ptr, ptr, C.c_int, C.c_int, C.c_int, C.c_int, i64, C.c_int, ptr],
@@ -336,7 +355,7 @@ EVAL_CONFUSION, EVAL_SAL, EVAL_DEPTH, EVAL_NORMALS, EVAL_EDGE = 0, 1, 2, 3, 4   
 EVAL_FROM_LOGITS, EVAL_FROM_MAP = 0, 1
 
 # Batch augmentation (csrc/augment.hip): additive exports under ABI 17, descriptor entry points like DESCS.  A table of its own: covered by
-# tests/test_gpu_augment.py.  The host copies of the table (table_host, off_host) are CPU tensors: `aug_call` passes their addresses.
+# tests/test_gpu_augment.py.  The host copies of the table (AugDesc._host_) are CPU tensors.
 AUGMENT = {"aug_select": AugDesc, "aug_image": AugDesc, "aug_labels": AugDesc}
 AUG_CANDS, AUG_COLS = 11, 40                                                      # MTT_AUG_* of include/mtt_hip.h
 (AUG_H, AUG_W, AUG_SH, AUG_SW, AUG_RESIZED, AUG_FLIP, AUG_NTEST, AUG_CHOSEN) = range(8)
@@ -346,12 +365,12 @@ AUG_PLAIN, AUG_DEPTH, AUG_NORMALS, AUG_HUMAN_PARTS = 0, 1, 2, 3
 E_BADARG, E_ALIGN, E_UNSUPPORTED = -1, -2, -3                                     # MTT_E_*
 
 # Cityscapes-3D batch preparation (csrc/cs3d.hip): additive exports under ABI 17 as well, covered by tests/test_gpu_cs3d.py.  The host
-# copies of the index tables (xtab_host, ytab_host) are CPU tensors: `cs3d_call` passes their addresses.
+# copies of the index tables (Cs3dDesc._host_) are CPU tensors.
 CS3D = {"cs3d_image": Cs3dDesc, "cs3d_labels": Cs3dDesc}
 CS3D_TILE_H, CS3D_TILE_W, CS3D_MAX_ROWS, CS3D_MAX_COLS = 16, 64, 208, 5440         # MTT_CS3D_* of include/mtt_hip.h
 
 # Rendering predictions (csrc/render.hip): additive exports under ABI 17 as well, covered by tests/test_gpu_render.py.  win_host is the
-# host copy of the window table, a CPU tensor: `render_call` passes its address.
+# host copy of the window table, a CPU tensor.
 RENDER = {"render_map": RenderDesc, "render_minmax": RenderDesc}
 RENDER_CLASS, RENDER_SIGMOID255, RENDER_SOFTMAX1_255, RENDER_NORMALS, RENDER_DEPTH = range(5)       # MTT_RENDER_* of include/mtt_hip.h
 RENDER_OUT_U8, RENDER_OUT_LUT1, RENDER_OUT_LUT3, RENDER_OUT_RGB3, RENDER_OUT_F32 = range(5)         # MTT_RENDER_OUT_*
@@ -360,13 +379,44 @@ RENDER_OUT_U8, RENDER_OUT_LUT1, RENDER_OUT_LUT3, RENDER_OUT_RGB3, RENDER_OUT_F32
 WS_QUERIES = {"gemm_colsum": GemmDesc, "chan_logits": ChanLogitDesc, "modulate_bwd": ModulateDesc, "ctr_dw": CtrDesc, "attn_msg_bwd": AttnMsgDesc, "loss": LossDesc,
               "chanattn_bwd": ChanAttnDesc, "detloss": DetLossDesc,
               "groupnorm": GnDesc, "dcn_col2im": DcnDesc, "fcos_bbox_post": BboxPostDesc, "fcos3d": Fcos3dDesc}
-EXPORTS = ["mtt_abi_version", "mtt_desc_size", "mtt_det_desc_size", "mtt_fcos3d_desc_size", "mtt_gemm_variant", "mtt_adam_chunk", "mtt_segcopy_chunk", "mtt_bn_reduce_ws_floats", "mtt_colsum_ws_floats", "mtt_rowscale_cast_colsum_ws_floats", "mtt_layernorm_bwd_ws_floats", "mtt_nms_ws_bytes", "mtt_det_decode_desc_size", "mtt_det_nms_ws_bytes", "mtt_eval_desc_size", "mtt_eval_ws_floats"] + ["mtt_%s_ws_floats" % n for n in WS_QUERIES] + ["mtt_" + n for n in list(DESCS) + list(POSITIONAL) + list(DESC_EXTRA) + list(POSTPROC) + list(EVAL)] + ["mtt_aug_desc_size"] + ["mtt_" + n for n in AUGMENT] + ["mtt_cs3d_desc_size"] + ["mtt_" + n for n in CS3D] + ["mtt_render_desc_size"] + ["mtt_" + n for n in RENDER]
+
+# the exports that belong to no family: symbol -> (restype, argtypes), the types as include/mtt_hip.h has them
+HELPERS = {
+    "mtt_abi_version": (C.c_int, []),
+    "mtt_desc_size": (C.c_size_t, [C.c_int]), "mtt_det_desc_size": (C.c_size_t, [C.c_int]),
+    **{sym: (C.c_size_t, []) for sym, idx, _ in SIZE_QUERIES if idx is None},
+    "mtt_gemm_variant": (C.c_int, [C.POINTER(GemmDesc)]), "mtt_adam_chunk": (C.c_int, []), "mtt_segcopy_chunk": (C.c_int, []),
+    "mtt_bn_reduce_ws_floats": (C.c_size_t, [i64, i32, i32]), "mtt_colsum_ws_floats": (C.c_size_t, [i64, i32]),
+    "mtt_rowscale_cast_colsum_ws_floats": (C.c_size_t, [i64, i32]), "mtt_layernorm_bwd_ws_floats": (C.c_size_t, [i64, i32]),
+    "mtt_nms_ws_bytes": (C.c_size_t, [C.c_int]), "mtt_det_nms_ws_bytes": (C.c_size_t, [C.POINTER(DetDecodeDesc)]),
+    "mtt_eval_ws_floats": (C.c_size_t, [C.POINTER(EvalDesc)]),
+}
+
+
+def _signatures():
+    """every export: symbol -> (restype, argtypes, descriptor struct the launchers fill or None)"""
+    sig = {sym: (res, at, None) for sym, (res, at) in HELPERS.items()}
+    for entry, st in WS_QUERIES.items():
+        sig["mtt_%s_ws_floats" % entry] = (C.c_size_t, [C.POINTER(st)], None)
+    for family in (DESCS, POSTPROC, EVAL, AUGMENT, CS3D, RENDER):
+        for name, st in family.items():
+            sig["mtt_" + name] = (C.c_int, [C.POINTER(st), ptr], st)
+    for name, at in POSITIONAL.items():
+        sig["mtt_" + name] = (C.c_int, at, None)
+    for name, (st, extra) in DESC_EXTRA.items():
+        sig["mtt_" + name] = (C.c_int, [C.POINTER(st)] + extra + [ptr], st)
+    return sig
+
+
+SIGNATURES = _signatures()
+EXPORTS = list(SIGNATURES)
 
 _lib = None
+_entry = {}                               # entry point name (no "mtt_") -> (function, descriptor struct or None), resolved by load()
 
 
 def load():
-    """Load the shared library (once) and verify ABI version + descriptor sizes.  Raises if absent."""
+    """Load the shared library (once), declare every export's signature and verify ABI version + descriptor sizes.  Raises if absent."""
     global _lib
     if _lib is not None:
         return _lib
@@ -375,168 +425,20 @@ def load():
             f"{LIB_PATH} not found: the HIP extension is required (no CPU/eager fallback). "
             "Build it with `python -c 'import __graft_entry__ as g; g.build()'`.")
     lib = C.CDLL(LIB_PATH)
-    lib.mtt_abi_version.restype = C.c_int
-    lib.mtt_desc_size.restype = C.c_size_t
-    lib.mtt_desc_size.argtypes = [C.c_int]
-    lib.mtt_bn_reduce_ws_floats.restype = C.c_size_t
-    lib.mtt_bn_reduce_ws_floats.argtypes = [i64, i32, i32]
-    lib.mtt_layernorm_bwd_ws_floats.restype = C.c_size_t
-    lib.mtt_layernorm_bwd_ws_floats.argtypes = [i64, i32]
-    lib.mtt_colsum_ws_floats.restype = C.c_size_t
-    lib.mtt_colsum_ws_floats.argtypes = [i64, i32]
+    entry = {}
+    for sym, (restype, argtypes, st) in SIGNATURES.items():
+        fn = getattr(lib, sym)
+        fn.restype, fn.argtypes = restype, argtypes
+        entry[sym[4:]] = (fn, st)
     if lib.mtt_abi_version() != ABI_VERSION:
         raise RuntimeError("libmtt_hip.so ABI version mismatch")
-    for idx, st in enumerate(_SIZE_INDEX):
-        if lib.mtt_desc_size(idx) != C.sizeof(st):
-            raise RuntimeError(f"descriptor layout mismatch for {st.__name__}: C {lib.mtt_desc_size(idx)} vs ctypes {C.sizeof(st)}")
-    lib.mtt_det_desc_size.restype = C.c_size_t
-    lib.mtt_det_desc_size.argtypes = [C.c_int]
-    for idx, st in enumerate(_DET_SIZE_INDEX):
-        if lib.mtt_det_desc_size(idx) != C.sizeof(st):
-            raise RuntimeError(f"descriptor layout mismatch for {st.__name__}: C {lib.mtt_det_desc_size(idx)} vs ctypes {C.sizeof(st)}")
-    lib.mtt_fcos3d_desc_size.restype = C.c_size_t
-    lib.mtt_fcos3d_desc_size.argtypes = []
-    if lib.mtt_fcos3d_desc_size() != C.sizeof(Fcos3dDesc):                           # ABI 15
-        raise RuntimeError(f"descriptor layout mismatch for Fcos3dDesc: C {lib.mtt_fcos3d_desc_size()} vs ctypes {C.sizeof(Fcos3dDesc)}")
-    lib.mtt_det_decode_desc_size.restype = C.c_size_t
-    lib.mtt_det_decode_desc_size.argtypes = []
-    if lib.mtt_det_decode_desc_size() != C.sizeof(DetDecodeDesc):                    # ABI 16
-        raise RuntimeError(f"descriptor layout mismatch for DetDecodeDesc: C {lib.mtt_det_decode_desc_size()} vs ctypes {C.sizeof(DetDecodeDesc)}")
-    lib.mtt_det_nms_ws_bytes.restype = C.c_size_t
-    lib.mtt_det_nms_ws_bytes.argtypes = [C.POINTER(DetDecodeDesc)]
-    lib.mtt_eval_desc_size.restype = C.c_size_t
-    lib.mtt_eval_desc_size.argtypes = []
-    if lib.mtt_eval_desc_size() != C.sizeof(EvalDesc):                               # ABI 17
-        raise RuntimeError(f"descriptor layout mismatch for EvalDesc: C {lib.mtt_eval_desc_size()} vs ctypes {C.sizeof(EvalDesc)}")
-    lib.mtt_eval_ws_floats.restype = C.c_size_t
-    lib.mtt_eval_ws_floats.argtypes = [C.POINTER(EvalDesc)]
-    lib.mtt_aug_desc_size.restype = C.c_size_t
-    lib.mtt_aug_desc_size.argtypes = []
-    if lib.mtt_aug_desc_size() != C.sizeof(AugDesc):
-        raise RuntimeError(f"descriptor layout mismatch for AugDesc: C {lib.mtt_aug_desc_size()} vs ctypes {C.sizeof(AugDesc)}")
-    lib.mtt_cs3d_desc_size.restype = C.c_size_t
-    lib.mtt_cs3d_desc_size.argtypes = []
-    if lib.mtt_cs3d_desc_size() != C.sizeof(Cs3dDesc):
-        raise RuntimeError(f"descriptor layout mismatch for Cs3dDesc: C {lib.mtt_cs3d_desc_size()} vs ctypes {C.sizeof(Cs3dDesc)}")
-    lib.mtt_render_desc_size.restype = C.c_size_t
-    lib.mtt_render_desc_size.argtypes = []
-    if lib.mtt_render_desc_size() != C.sizeof(RenderDesc):
-        raise RuntimeError(f"descriptor layout mismatch for RenderDesc: C {lib.mtt_render_desc_size()} vs ctypes {C.sizeof(RenderDesc)}")
-    for name, st in (list(DESCS.items()) + list(POSTPROC.items()) + list(EVAL.items()) + list(AUGMENT.items()) + list(CS3D.items())
-                     + list(RENDER.items())):
-        fn = getattr(lib, "mtt_" + name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.POINTER(st), ptr]
-    for name, at in POSITIONAL.items():
-        fn = getattr(lib, "mtt_" + name)
-        fn.restype = C.c_int
-        fn.argtypes = at
-    for name, (st, extra) in DESC_EXTRA.items():
-        fn = getattr(lib, "mtt_" + name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.POINTER(st)] + extra + [ptr]
+    for sym, idx, st in SIZE_QUERIES:
+        size = getattr(lib, sym)() if idx is None else getattr(lib, sym)(idx)
+        if size != C.sizeof(st):
+            raise RuntimeError(f"descriptor layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
+    _entry.update(entry)
     _lib = lib
     return lib
-
-
-def ws_floats(entry, **fields):
-    """mtt_<entry>_ws_floats(desc) for the geometry in `fields` (ints only; pointer fields stay NULL)."""
-    lib = load()
-    desc = WS_QUERIES[entry]()
-    for k, v in fields.items():
-        setattr(desc, k, v)
-    fn = getattr(lib, "mtt_%s_ws_floats" % entry)
-    fn.restype = C.c_size_t
-    fn.argtypes = [C.POINTER(WS_QUERIES[entry])]
-    return int(fn(C.byref(desc)))
-
-
-def det_nms_ws_bytes(batch, classes, cands):
-    """mtt_det_nms_ws_bytes for `batch` images, `classes` classes and `cands` candidates per image"""
-    lib = load()
-    desc = DetDecodeDesc()
-    desc.B, desc.C, desc.N = int(batch), int(classes), int(cands)
-    return int(lib.mtt_det_nms_ws_bytes(C.byref(desc)))
-
-
-def eval_ws_floats(kind, batch, pixels):
-    """mtt_eval_ws_floats for meter kind `kind` on `batch` images of `pixels` pixels"""
-    lib = load()
-    desc = EvalDesc()
-    desc.kind, desc.B, desc.HW = int(kind), int(batch), int(pixels)
-    return int(lib.mtt_eval_ws_floats(C.byref(desc)))
-
-
-def aug_call(name, host=(), stream=None, **fields):
-    """mtt_<name> of AUGMENT.  Device tensors in `fields` become device pointers (a CPU tensor raises, as everywhere); the fields named in
-    `host` are the host copies the entry point validates and take CPU tensors.  Returns the status instead of raising on MTT_E_BADARG, so
-    that a caller can tell a refused table from a failed launch; every other non-zero status raises.  stream: torch's current one by default."""
-    lib = load()
-    desc = AugDesc()
-    for k, v in fields.items():
-        if isinstance(v, torch.Tensor):
-            if k in host:
-                if v.is_cuda:
-                    raise RuntimeError(f"{k} is the host copy of the table and must be a CPU tensor")
-                setattr(desc, k, v.data_ptr())
-            else:
-                setattr(desc, k, _addr(v))
-        elif isinstance(v, (list, tuple)):
-            arr = getattr(desc, k)
-            for i, e in enumerate(v):
-                arr[i] = e
-        elif v is not None:
-            setattr(desc, k, v)
-    rc = getattr(lib, "mtt_" + name)(C.byref(desc), _stream() if stream is None else stream)
-    if rc != 0 and rc != E_BADARG:
-        raise RuntimeError(f"mtt_{name} failed with status {rc}" + (" (argument error)" if rc < 0 else " (hipError_t)"))
-    return rc
-
-
-def cs3d_call(name, stream=None, **fields):
-    """mtt_<name> of CS3D.  Device tensors become device pointers (a CPU tensor raises); xtab_host / ytab_host take CPU tensors.  Returns 0 or a negative MTT_E_* status (a refused descriptor, nothing
-    launched); a hipError_t raises."""
-    lib = load()
-    desc = Cs3dDesc()
-    for k, v in fields.items():
-        if isinstance(v, torch.Tensor):
-            if k in ("xtab_host", "ytab_host"):
-                if v.is_cuda:
-                    raise RuntimeError(f"{k} is the host copy of the table and must be a CPU tensor")
-                setattr(desc, k, v.data_ptr())
-            else:
-                setattr(desc, k, _addr(v))
-        elif isinstance(v, (list, tuple)):
-            arr = getattr(desc, k)
-            for i, e in enumerate(v):
-                arr[i] = e
-        elif v is not None:
-            setattr(desc, k, v)
-    rc = getattr(lib, "mtt_" + name)(C.byref(desc), _stream() if stream is None else stream)
-    if rc > 0:
-        raise RuntimeError(f"mtt_{name} failed with status {rc} (hipError_t)")
-    return rc
-
-
-def render_call(name, stream=None, **fields):
-    """mtt_<name> of RENDER.  Device tensors become device pointers (a CPU tensor raises); win_host takes a CPU tensor.  Returns 0 or a
-    negative MTT_E_* status (a refused descriptor, nothing launched); a hipError_t raises."""
-    lib = load()
-    desc = RenderDesc()
-    for k, v in fields.items():
-        if isinstance(v, torch.Tensor):
-            if k == "win_host":
-                if v.is_cuda:
-                    raise RuntimeError("win_host is the host copy of the window table and must be a CPU tensor")
-                setattr(desc, k, v.data_ptr())
-            else:
-                setattr(desc, k, _addr(v))
-        elif v is not None:
-            setattr(desc, k, v)
-    rc = getattr(lib, "mtt_" + name)(C.byref(desc), _stream() if stream is None else stream)
-    if rc > 0:
-        raise RuntimeError(f"mtt_{name} failed with status {rc} (hipError_t)")
-    return rc
 
 
 def dtype_code(t):
@@ -559,58 +461,89 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def gemm_variant(**kw):
-    """Kernel mtt_gemm would dispatch these descriptor fields to (0 general 128x128, 3 LDS-DMA 256x256, 6 token-major weight gradient,
-    8 LDS-DMA 256x256 on split operands; < 0: no kernel takes them)."""
-    lib = load()
-    desc = GemmDesc()
-    for k, v in kw.items():
-        if k == "conv":
+def _fill(desc, fields, cpu_ok=False):
+    """Fill descriptor `desc` from keyword fields and return it.  A tensor becomes its device address (a CPU tensor raises, unless cpu_ok:
+    the descriptor is only inspected); in a field the struct lists in `_host_` it is the host copy the entry point validates and must be
+    a CPU tensor.  conv={...} fills the nested mtt_conv_geom, a list or tuple fills an array element by element, None leaves the field
+    NULL, ints (addresses included) and floats are assigned as they are."""
+    host = getattr(desc, "_host_", ())
+    for k, v in fields.items():
+        if type(v) is int or type(v) is float:             # most fields by far: ahead of the costlier isinstance tests
+            setattr(desc, k, v)
+        elif isinstance(v, torch.Tensor):
+            if k in host:
+                if v.is_cuda:
+                    raise RuntimeError(f"{k} is the host copy of the table and must be a CPU tensor")
+                setattr(desc, k, v.data_ptr())
+            else:
+                setattr(desc, k, v.data_ptr() if cpu_ok else _addr(v))
+        elif v is None:
+            continue
+        elif k == "conv":
             for ck, cv in v.items():
                 setattr(desc.conv, ck, int(cv))
-        elif isinstance(v, torch.Tensor):
-            setattr(desc, k, v.data_ptr())
-        elif v is not None:
+        elif isinstance(v, (list, tuple)):
+            arr = getattr(desc, k)
+            for i, e in enumerate(v):
+                arr[i] = _addr(e) if isinstance(e, torch.Tensor) else e
+        else:
             setattr(desc, k, v)
-    lib.mtt_gemm_variant.restype = C.c_int
-    lib.mtt_gemm_variant.argtypes = [C.POINTER(GemmDesc)]
-    return lib.mtt_gemm_variant(C.byref(desc))
+    return desc
+
+
+def _query(symbol, st, fields, cpu_ok=False):
+    """what `symbol(const desc*)` answers for a descriptor `st` filled from `fields`"""
+    return int(getattr(load(), symbol)(C.byref(_fill(st(), fields, cpu_ok))))
+
+
+def ws_floats(entry, **fields):
+    """mtt_<entry>_ws_floats(desc) for the geometry in `fields` (ints only; pointer fields stay NULL)."""
+    return _query("mtt_%s_ws_floats" % entry, WS_QUERIES[entry], fields)
+
+
+def det_nms_ws_bytes(batch, classes, cands):
+    """mtt_det_nms_ws_bytes for `batch` images, `classes` classes and `cands` candidates per image"""
+    return _query("mtt_det_nms_ws_bytes", DetDecodeDesc, dict(B=int(batch), C=int(classes), N=int(cands)))
+
+
+def eval_ws_floats(kind, batch, pixels):
+    """mtt_eval_ws_floats for meter kind `kind` on `batch` images of `pixels` pixels"""
+    return _query("mtt_eval_ws_floats", EvalDesc, dict(kind=int(kind), B=int(batch), HW=int(pixels)))
+
+
+def gemm_variant(**kw):
+    """Kernel mtt_gemm would dispatch these descriptor fields to (0 general 128x128, 3 LDS-DMA 256x256, 6 token-major weight gradient,
+    8 LDS-DMA 256x256 on split operands; < 0: no kernel takes them).  Only inspects the descriptor, so CPU tensors are accepted."""
+    return _query("mtt_gemm_variant", GemmDesc, kw, cpu_ok=True)
+
+
+def _launch(name, kw, stream=None):
+    """the status of mtt_<name> for the fields, `args` or `xargs` in kw, on `stream` (torch's current one by default)"""
+    load()
+    fn, st = _entry[name]
+    if st is None:
+        return fn(*[(_addr(a) if isinstance(a, torch.Tensor) else a) for a in kw["args"]], _stream() if stream is None else stream)
+    xargs = [(_addr(a) if isinstance(a, torch.Tensor) else a) for a in kw.pop("xargs", ())]
+    desc = _fill(st(), kw)
+    return fn(C.byref(desc), *xargs, _stream() if stream is None else stream)
 
 
 def call(name, **kw):
     """Launch `mtt_<name>`; tensors in `kw` become device pointers.  For descriptor entry points
-    nested dict `conv={...}` fills mtt_conv_geom.  Positional entry points take `args=[...]`."""
-    lib = load()
-    fn = getattr(lib, "mtt_" + name)
-    if name in POSITIONAL:
-        args = [(_addr(a) if isinstance(a, torch.Tensor) else a) for a in kw["args"]]
-        rc = fn(*args, _stream())
-    else:
-        extra = None
-        if name in DESC_EXTRA:
-            st, _ = DESC_EXTRA[name]
-            desc = st()
-            extra = [(_addr(a) if isinstance(a, torch.Tensor) else a) for a in kw["xargs"]]
-        else:
-            desc = (POSTPROC[name] if name in POSTPROC else EVAL[name] if name in EVAL else DESCS[name])()
-        for k, v in kw.items():
-            if k == "xargs":
-                continue
-            if k == "in":
-                k = "in_"
-            if k == "conv":
-                for ck, cv in v.items():
-                    setattr(desc.conv, ck, int(cv))
-            elif isinstance(v, torch.Tensor):
-                setattr(desc, k, _addr(v))
-            elif v is None:
-                setattr(desc, k, None)
-            elif isinstance(v, (list, tuple)):
-                arr = getattr(desc, k)
-                for i, e in enumerate(v):
-                    arr[i] = _addr(e) if isinstance(e, torch.Tensor) else e
-            else:
-                setattr(desc, k, v)
-        rc = fn(C.byref(desc), *extra, _stream()) if extra is not None else fn(C.byref(desc), _stream())
+    nested dict `conv={...}` fills mtt_conv_geom.  Positional entry points take `args=[...]`, those of
+    DESC_EXTRA their extra arguments in `xargs=[...]`.  Raises on any non-zero status."""
+    rc = _launch(name, kw)
     if rc != 0:
         raise RuntimeError(f"mtt_{name} failed with status {rc}" + (" (argument error)" if rc < 0 else " (hipError_t)"))
+
+
+def status_call(name, stream=None, **fields):
+    """Launch `mtt_<name>` of AUGMENT, CS3D or RENDER, whose entry points validate their descriptor on the host.  Returns 0 or the negative
+    MTT_E_* status (a refused descriptor, nothing launched), so that a caller can tell it from a failed launch; a hipError_t raises."""
+    rc = _launch(name, fields, stream)
+    if rc > 0:
+        raise RuntimeError(f"mtt_{name} failed with status {rc} (hipError_t)")
+    return rc
+
+
+aug_call = cs3d_call = render_call = status_call

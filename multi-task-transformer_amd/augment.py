@@ -205,7 +205,6 @@ class DeviceAugment:
         off_host = torch.empty((2, B), dtype=torch.int64, pin_memory=True)       # row 0: one channel per pixel, row 1: three
         off_host.numpy()[0], off_host.numpy()[1] = start, 3 * start
         table, off = table_host.to(dev, non_blocking=True), off_host.to(dev, non_blocking=True)
-        host = ("table_host", "off_host")
 
         def packed(k):
             c = CHANNELS.get(k, 1)
@@ -217,8 +216,9 @@ class DeviceAugment:
                         table=table, table_host=table_host, B=B, h=h, w=w)
 
         def launch(name, **kw):
-            if _lib.aug_call(name, host=host, **kw) != 0:
-                raise RuntimeError(f"mtt_{name}: the parameter table was refused (MTT_E_BADARG)")
+            rc = _lib.aug_call(name, **kw)
+            if rc != 0:
+                raise RuntimeError(f"mtt_{name}: the descriptor or its parameter table was refused (status {rc})")
 
         if (params.n_test != 0).any():
             launch("aug_select", cat_max_ratio=self.cat_max_ratio, **packed("semseg"))

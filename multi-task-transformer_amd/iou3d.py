@@ -3,8 +3,6 @@ arguments and results) on the HIP kernels of csrc/iou3d.hip.  Boxes are [x1, y1,
 
 Unlike the reference (which copies the N x N/64 suppression masks to the host and reduces them there), the greedy pass runs on the
 device; the only host synchronisation is reading the number of kept boxes to size the returned index tensor."""
-import ctypes
-
 import torch
 
 from . import _lib, ops
@@ -29,9 +27,7 @@ def boxes_iou_bev(boxes_a, boxes_b):
 
 
 def nms_ws_bytes(n):
-    lib = _lib.load()
-    lib.mtt_nms_ws_bytes.restype = ctypes.c_size_t
-    return int(lib.mtt_nms_ws_bytes(int(n)))
+    return int(_lib.load().mtt_nms_ws_bytes(int(n)))
 
 
 def _nms_sorted(boxes, thresh, rotated):

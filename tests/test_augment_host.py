@@ -117,7 +117,7 @@ def test_cpu_tensors_raise():
     with pytest.raises(RuntimeError):
         aug([sample])
     with pytest.raises(RuntimeError):
-        mtt_amd._lib.aug_call("aug_image", host=("table_host",), src=torch.zeros(8), table_host=torch.zeros(40, dtype=torch.int32))
+        mtt_amd._lib.aug_call("aug_image", src=torch.zeros(8), table_host=torch.zeros(40, dtype=torch.int32))
 
 
 def test_class_share_test_needs_semseg():
@@ -150,7 +150,7 @@ def test_host_check_refuses_a_bad_table_without_a_device():
     fake = lambda t: t.data_ptr()                          # noqa: E731  (never dereferenced: every call below is refused by the host check)
     def call(table, numel=8 * 8 * 3, offset=0):
         off[0] = offset
-        return lib.aug_call("aug_image", host=("table_host", "off_host"), table_host=table, off_host=off, src=fake(good), off=fake(good), table=fake(good),
+        return lib.aug_call("aug_image", table_host=table, off_host=off, src=fake(good), off=fake(good), table=fake(good),
                             out=fake(good), src_numel=numel, B=1, h=8, w=8, C=3, stream=0)
     for col, val in ((lib.AUG_H, 9), (lib.AUG_W, 0), (lib.AUG_SH, 40000), (lib.AUG_CAND_Y + 3, 1), (lib.AUG_CAND_X, -1), (lib.AUG_CHOSEN, 11),
                      (lib.AUG_HDELTA, 18), (lib.AUG_FLIP, 2), (lib.AUG_NTEST, 5)):

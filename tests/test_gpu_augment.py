@@ -179,7 +179,7 @@ def test_a_bad_table_row_is_refused_and_nothing_is_launched():
     out = torch.full((3, 1, 64, 56), -7.0, device="cuda:0")
 
     def call(table_host, off_h=off_host, numel=flat.numel()):
-        return L.aug_call("aug_labels", host=("table_host", "off_host"), src=flat, src_numel=numel, C=1, off=off_h.to("cuda:0"), off_host=off_h,
+        return L.aug_call("aug_labels", src=flat, src_numel=numel, C=1, off=off_h.to("cuda:0"), off_host=off_h,
                           table=good.to("cuda:0"), table_host=table_host, out=out, B=3, h=64, w=56, kind=L.AUG_DEPTH, fill=0.0, depth_ignore=1)
 
     for col, val in ((L.AUG_H, 65), (L.AUG_W, 0), (L.AUG_SH, 1 << 20), (L.AUG_CAND_Y + 10, 1), (L.AUG_CAND_X + 2, -3), (L.AUG_CHOSEN, 11), (L.AUG_NTEST, 3)):

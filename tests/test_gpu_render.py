@@ -440,6 +440,16 @@ def test_no_synchronisation_and_graph_replay():
             assert torch.equal(raws[t].view(torch.uint8), want["raw_" + t].view(torch.uint8)), t
 
 
+@pytest.mark.gpu
+def test_a_device_tensor_as_the_host_copy_raises():
+    """win_host is the copy the entry point reads on the host: a device tensor there is refused by the binding, before anything is launched"""
+    _need_gpu()
+    import mtt_amd
+    win = torch.zeros(4, dtype=torch.int64, device="cuda:0")
+    with pytest.raises(RuntimeError, match="must be a CPU tensor"):
+        mtt_amd._lib.render_call("render_map", win_host=win)
+
+
 # ---- 6. coverage of the binding table -----------------------------------------------------------------------------------------------------
 def test_every_render_entry_point_is_covered():
     """the assertion tests/test_parity_comparator.py makes for DESCS | POSITIONAL | DESC_EXTRA, for the table of its own the rendering entry

@@ -23,7 +23,60 @@ def test_library_loads_and_exports_header_symbols():
     assert declared, "no declarations parsed"
     for sym in sorted(declared):
         assert hasattr(lib, sym), f"{sym} declared in mtt_hip.h but not exported"
-    assert set(mtt_amd._lib.EXPORTS) <= declared
+    assert set(mtt_amd._lib.EXPORTS) == declared
+    # every prototype against the signature load() declared: return type, parameter count and each parameter's kind
+    import ctypes as C
+    protos = re.findall(r"^\s*(int|size_t)\s+(mtt_\w+)\s*\(([^)]*)\)\s*;", re.sub(r"/\*.*?\*/", "", header, flags=re.S), flags=re.M)
+    assert len(protos) == len(declared) and {p[1] for p in protos} == declared
+    scalars = {"int64_t": C.c_int64, "int": C.c_int, "int32_t": C.c_int32, "float": C.c_float, "size_t": C.c_size_t}
+    assert C.sizeof(C.c_int) == C.sizeof(C.c_int32) == 4
+    for ret, sym, params in protos:
+        fn = getattr(lib, sym)
+        assert fn.argtypes is not None, f"{sym} has no declared argtypes"
+        assert fn.restype is {"int": C.c_int, "size_t": C.c_size_t}[ret], sym
+        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
+        assert len(fn.argtypes) == len(params), sym
+        for at, p in zip(fn.argtypes, params):
+            if "*" in p:
+                assert at is C.c_void_p or issubclass(at, C._Pointer), (sym, p, at)
+            else:
+                ctype = p.replace("const ", "").split()[0]
+                assert at is scalars[ctype], (sym, p, at)
+
+
+def _cpu_tensor_calls():
+    """a CPU tensor in a device field, through each launcher"""
+    import mtt_amd
+    lib, x = mtt_amd._lib, torch.zeros(8)
+    return [lambda: lib.call("gemm", A=x), lambda: lib.call("bn_stats", x=x, xargs=[0]), lambda: lib.call("bn_stats", xargs=[x]),
+            lambda: lib.call("fcos_bbox_post", x=[x]), lambda: lib.aug_call("aug_image", src=x, stream=0),
+            lambda: lib.cs3d_call("cs3d_image", src=x, stream=0), lambda: lib.render_call("render_map", src=x, stream=0)]
+
+
+def test_descriptor_filler():
+    """`_lib._fill`, the one function that turns keyword fields into a descriptor (no library needed for the plain descriptors)"""
+    import mtt_amd
+    lib = mtt_amd._lib
+    geom = dict(H=5, W=7, C=3, Cp=8, dil=2, flip=1)
+    d = lib._fill(lib.GemmDesc(), dict(conv=geom, A=0x1230, B=None, alpha=0.5, M=3, lda=1 << 40))
+    assert {k: getattr(d.conv, k) for k in geom} == geom
+    assert (d.A, d.B, d.alpha, d.M, d.lda) == (0x1230, None, 0.5, 3, 1 << 40)
+    assert all(not getattr(d, k) for k, _ in lib.GemmDesc._fields_ if k not in ("conv", "A", "alpha", "M", "lda")), "a field nobody named is set"
+    assert lib._fill(lib.ResizeDesc(), {"in": 0x40}).in_ == 0x40
+    d = lib._fill(lib.BboxPostDesc(), dict(x=[16, 32, 48]))
+    assert list(d.x) == [16, 32, 48] + [None] * 5 and list(d.ldx) == [0] * 8 and list(d.dx) == [None] * 8
+    assert list(lib._fill(lib.AugDesc(), dict(mean=[0.25, 0.5, 0.75])).mean) == [0.25, 0.5, 0.75]
+    for launch in _cpu_tensor_calls():
+        with pytest.raises(RuntimeError, match="device memory only"):
+            launch()
+    x = torch.zeros(8)
+    assert lib.gemm_variant(A=x, B=x, D=x, M=8, N=1, K=1) is not None                       # inspects the descriptor only: CPU tensors pass
+    assert lib._fill(lib.GemmDesc(), dict(A=x), cpu_ok=True).A == x.data_ptr()
+    hosts = {lib.AugDesc: ("table_host", "off_host"), lib.Cs3dDesc: ("xtab_host", "ytab_host"), lib.RenderDesc: ("win_host",)}
+    for st, fields in hosts.items():
+        assert st._host_ == fields
+        for k in fields:
+            assert getattr(lib._fill(st(), {k: x}), k) == x.data_ptr(), k
 
 
 def test_no_cpu_fallback():
