@@ -8,8 +8,7 @@ keep=False (no statistics, log-sum-exp or GELU' side output is written then); In
 runs on the same two bodies.  The front of cal_task_feature is shared the same way (_task_features); its tail and the
 heads keep a fused inference schedule of their own (TaskPrompter._fuse_tail, taskprompter.run_heads).  With a
 backward, autograd carries only the fp32 residual stream, the logit side channels and the decoder feature maps
-between Functions.  Round 1 attention backward materialises P per (batch, head) with the batched GEMM + row-softmax
-kernels (no N x N tensor ever leaves the backward), see DESIGN.md.
+between Functions.
 """
 import math
 
@@ -77,29 +76,46 @@ def _to_bwd(t, prec):
     return ops.cast_rows(t2, torch.bfloat16).view(t.shape)
 
 
-def _wgrad(dy, x, N, Kp, prec, rows=None, lda=None, ldb=None):
-    """dW[N, Kp] = dy[rows, :N]^T @ x[rows, :Kp]  (both operands row-contiguous views).
+def _slab_gemm(A, B, N, W, rows, cut, prec, lda, ldb, Z=None, a_zo=0, b_zo=0, a0=0, b0=0, b_op=OP_R, conv=None):
+    """THE weight-gradient launch: D[z] [N, W] fp32 = A[z]^T B[z], reduced over `rows` rows of two row-contiguous operands (row pitches
+    lda / ldb; task z starts a0 + z * a_zo / b0 + z * b_zo elements into them; b_op = OP_CONV_R gathers B's nine taps by its `conv`
+    geometry).  cut = None: one launch.  cut = (n, c), the callers' policy: the reduction goes over the GEMM's batch dimension as n slices
+    of c rows, with one more launch for the rows behind n * c, into fp32 slabs that are summed afterwards (split-K: fills the 256 CUs
+    instead of running thousands of K steps in a handful of workgroups).  Z = None: one matrix -> [N, W], its slices a one-level batch;
+    otherwise -> [Z, N, W], (task, slice) a two-level batch."""
+    kw = dict(a_op=OP_R, b_op=b_op, lda=lda, ldb=ldb, ldd=W, **({} if conv is None else dict(conv=conv)))
+    lead, task = ((), {}) if Z is None else ((Z,), dict(batch=Z, a_zo=a_zo, b_zo=b_zo))
+    A, B = (A.reshape(-1)[a0:] if a0 else A), (B.reshape(-1)[b0:] if b0 else B)
+    if cut is None:
+        D = torch.empty(*lead, N, W, dtype=torch.float32, device=A.device)
+        return _gemm(A, B, D, N, W, rows, prec, **kw, **task, **(dict(d_zo=N * W) if task else {}))
+    n, c = cut
+    rem = rows - n * c
+    slabs = torch.empty(*lead, n + (1 if rem else 0), N, W, dtype=torch.float32, device=A.device)
+    d_zo = slabs.shape[-3] * N * W
+    if Z is None:
+        _gemm(A, B, slabs, N, W, c, prec, batch=n, a_zo=c * lda, b_zo=c * ldb, d_zo=N * W, **kw)
+        if rem:
+            _gemm(A[n * c:], B[n * c:], slabs[n], N, W, rem, prec, **kw)
+    else:
+        _gemm(A, B, slabs, N, W, c, prec, batch=Z * n, batch_inner=n, a_zo=a_zo, a_zi=c * lda, b_zo=b_zo, b_zi=c * ldb, d_zo=d_zo, d_zi=N * W, **kw)
+        if rem:
+            _gemm(A.reshape(-1)[n * c * lda:], B.reshape(-1)[n * c * ldb:], slabs[:, n], N, W, rem, prec, d_zo=d_zo, **task, **kw)
+    return slabs.sum(-3)
 
-    When the output has only a few 128x128 tiles but the reduction (tokens / pixels) is long, the reduction is split
-    over the GEMM's batch dimension into fp32 slabs that are summed afterwards (split-K: fills the 256 CUs instead of
-    running thousands of K steps in a handful of workgroups)."""
+
+def _wgrad(dy, x, N, Kp, prec, rows=None, lda=None, ldb=None):
+    """dW[N, Kp] = dy[rows, :N]^T @ x[rows, :Kp]  (both operands row-contiguous views), sliced when the output has only a few 128x128
+    tiles but the reduction (tokens / pixels) is long."""
     rows = rows if rows is not None else dy.shape[0]
-    lda, ldb = lda or dy.stride(0), ldb or x.stride(0)
+    cut = None
     tiles = -(-N // 128) * -(-Kp // 128)
     if tiles < 96 and rows >= SPLITK_MIN_ROWS:
         # two workgroups per CU (the kernel's LDS allows it): a handful of output tiles over a million pixel rows (the head predictions'
         # weight gradients: 3 tiles) is pure streaming of x — 64 slices left three quarters of the CUs without a workgroup
-        Z = max(2, min(WGRAD_MAX_SLICES, WGRAD_TARGET_WGS // tiles, max(2, rows // 512)))
-        c = rows // Z
-        rem = rows - c * Z
-        slabs = torch.empty(Z + (1 if rem else 0), N, Kp, dtype=torch.float32, device=dy.device)
-        _gemm(dy, x, slabs, N, Kp, c, prec, a_op=OP_R, b_op=OP_R, lda=lda, ldb=ldb, ldd=Kp, batch=Z, a_zo=c * lda, b_zo=c * ldb,
-              d_zo=N * Kp)
-        if rem:
-            _gemm(dy[c * Z:], x[c * Z:], slabs[Z], N, Kp, rem, prec, a_op=OP_R, b_op=OP_R, lda=lda, ldb=ldb, ldd=Kp)
-        return slabs.sum(0)
-    dW = torch.empty(N, Kp, dtype=torch.float32, device=dy.device)
-    return _gemm(dy, x, dW, N, Kp, rows, prec, a_op=OP_R, b_op=OP_R, lda=lda, ldb=ldb, ldd=Kp)
+        n = max(2, min(WGRAD_MAX_SLICES, WGRAD_TARGET_WGS // tiles, max(2, rows // 512)))
+        cut = (n, rows // n)
+    return _slab_gemm(dy, x, N, Kp, rows, cut, prec, lda or dy.stride(0), ldb or x.stride(0))
 
 
 SPLIT_TARGET_WGS, SPLIT_ROW_UNIT = 1024, 512        # (tests lower SPLIT_ROW_UNIT to exercise the sliced paths on miniature maps)
@@ -116,43 +132,18 @@ def _n_splits(tiles, units, max_splits=16):
 def _wgrad_batched(dy, x, N, Kp, M, prec, Z, lda, ldb, a_zo, b_zo, a0=0, b0=0):
     """dW[z] = dy[z]^T x[z] for z < Z (row-contiguous operands, element offsets a0 + z*a_zo / b0 + z*b_zo): one launch over
     (task, reduction slice) with fp32 slabs summed afterwards when the tile count alone cannot fill the chip."""
-    A = dy.reshape(-1)[a0:] if a0 else dy
-    B = x.reshape(-1)[b0:] if b0 else x
     p256 = (-(-N // 256)) * (-(-Kp // 256))
+    cut = None
     if (prec.name == "bf16" and FAST_BWD and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and M >= SPLITK_MIN_ROWS
             and min(N, Kp) >= FAST_MIN_DIM and 100 * N * Kp >= 45 * p256 * 65536 and lda % 8 == 0 and ldb % 8 == 0):
         # token-major LDS-DMA kernel (the policy of mtt_gemm picks it for these launches): 256 x 256 tiles, slices chosen to fill the
         # 256 CUs in whole rounds.  N = 300 / 350 outputs waste 41-53 % of a tile pair and it still wins: 432 vs 697 us (fea_decode),
         # 313 vs 424 (fea_fuse[0]), 232 vs 286 (fea_fuse[4]) at B = 63 (profiles/r03_dec_wgrad_bench_h.log)
-        S = _tn_splits(Z * p256, M)
-        c = (M // S) // 64 * 64
-        if c >= 512:
-            nz = M // c
-            rem = M - nz * c
-            slabs = torch.empty(Z, nz + (1 if rem else 0), N, Kp, dtype=torch.float32, device=dy.device)
-            SS = slabs.shape[1]
-            _gemm(A, B, slabs, N, Kp, c, prec, a_op=OP_R, b_op=OP_R, lda=lda, ldb=ldb, ldd=Kp, batch=Z * nz, batch_inner=nz,
-                  a_zo=a_zo, a_zi=c * lda, b_zo=b_zo, b_zi=c * ldb, d_zo=SS * N * Kp, d_zi=N * Kp)
-            if rem:
-                _gemm(dy.reshape(-1)[a0 + nz * c * lda:], x.reshape(-1)[b0 + nz * c * ldb:], slabs[:, nz], N, Kp, rem, prec, a_op=OP_R,
-                      b_op=OP_R, lda=lda, ldb=ldb, ldd=Kp, batch=Z, a_zo=a_zo, b_zo=b_zo, d_zo=SS * N * Kp)
-            return slabs.sum(1)
-    tiles = Z * (-(-N // 128)) * (-(-Kp // 128))
-    S = _n_splits(tiles, M // SPLIT_ROW_UNIT)
-    if S == 1:
-        dW = torch.empty(Z, N, Kp, dtype=torch.float32, device=dy.device)
-        _gemm(A, B, dW, N, Kp, M, prec, a_op=OP_R, b_op=OP_R, lda=lda, ldb=ldb, ldd=Kp, batch=Z, a_zo=a_zo, b_zo=b_zo, d_zo=N * Kp)
-        return dW
-    c = (M // S) // 8 * 8
-    rem = M - c * S
-    slabs = torch.empty(Z, S + (1 if rem else 0), N, Kp, dtype=torch.float32, device=dy.device)
-    SS = slabs.shape[1]
-    _gemm(A, B, slabs, N, Kp, c, prec, a_op=OP_R, b_op=OP_R, lda=lda, ldb=ldb, ldd=Kp, batch=Z * S, batch_inner=S,
-          a_zo=a_zo, a_zi=c * lda, b_zo=b_zo, b_zi=c * ldb, d_zo=SS * N * Kp, d_zi=N * Kp)
-    if rem:
-        _gemm(dy.reshape(-1)[a0 + c * S * lda:], x.reshape(-1)[b0 + c * S * ldb:], slabs[:, S], N, Kp, rem, prec, a_op=OP_R, b_op=OP_R,
-              lda=lda, ldb=ldb, ldd=Kp, batch=Z, a_zo=a_zo, b_zo=b_zo, d_zo=SS * N * Kp)
-    return slabs.sum(1)
+        cut = _tn_cut(Z * p256, M)
+    if cut is None:
+        S = _n_splits(Z * (-(-N // 128)) * (-(-Kp // 128)), M // SPLIT_ROW_UNIT)
+        cut = (S, (M // S) // 8 * 8) if S > 1 else None
+    return _slab_gemm(dy, x, N, Kp, M, cut, prec, lda, ldb, Z, a_zo, b_zo, a0, b0)
 
 
 def _pad_last(t, width):
@@ -178,26 +169,42 @@ def _tn_splits(tiles, rows, max_splits=32):
     return best
 
 
+def _tn_cut(tiles, rows):
+    """_tn_splits as a cut of _slab_gemm: slices of whole 64-row steps, the rows they leave over included; None (no such slicing) below
+    512 rows per slice."""
+    c = (rows // _tn_splits(tiles, rows)) // 64 * 64
+    return (rows // c, c) if c >= 512 else None
+
+
+def _image_splits(Z, N, W, B, bf16):
+    """Reduction slices of the 3x3 conv's weight gradient, Z matrices [N, W = 9 * pitch(Ci)] over B images: slices are whole images
+    (the gather decomposes pixel -> (y, x)), so a divisor of B.  bf16: both operands are bf16 under bf16 arithmetic."""
+    S = _n_splits(Z * (-(-N // 128)) * (-(-W // 128)), B)
+    p256 = Z * (-(-N // 256)) * (-(-W // 256))
+    if bf16 and p256 >= 64 and 100 * N * W >= 45 * (-(-N // 256)) * (-(-W // 256)) * 65536:
+        # the token-major kernel takes this launch (256 x 256 tiles, one per CU): slice the pixels so that the workgroups fill whole
+        # rounds of the 256 CUs — InvPT's 576-channel convs at 128 x 128: 378 tiles = 1.48 rounds, two slices = 2.95
+        best = None
+        for cand in range(1, min(B, 8) + 1):
+            if B % cand:
+                continue
+            cost = -(-p256 * cand // N_CUS) / cand + 0.02 * (cand - 1)        # rounds per slice + the slab it writes and re-reads
+            if best is None or cost < best[0] - 1e-9:
+                best = (cost, cand)
+        S = best[1]
+    while B % S:
+        S -= 1
+    return S
+
+
 def _wgrad_tn(dy, x, N, Kp, prec):
     """dW[N, Kp] = dy^T x straight from the token-major operands (mtt_gemm MTT_OP_R x MTT_OP_R -> gemm_tn_kernel: LDS-DMA of the rows as
     they sit in memory + LDS transpose reads), the token reduction sliced over the batch dimension into fp32 slabs when the 256 x 256
     output tiles alone cannot fill the chip."""
     rows = dy.shape[0]
-    lda, ldb = dy.stride(0), x.stride(0)
     tiles = -(-N // 256) * -(-Kp // 256)
-    if tiles < 192 and rows >= 4096:
-        S = _tn_splits(tiles, rows)
-        c = (rows // S) // 64 * 64
-        if c >= 512:
-            nz = rows // c
-            rem = rows - nz * c
-            slabs = torch.empty(nz + (1 if rem else 0), N, Kp, dtype=torch.float32, device=dy.device)
-            _gemm(dy, x, slabs, N, Kp, c, prec, a_op=OP_R, b_op=OP_R, lda=lda, ldb=ldb, ldd=Kp, batch=nz, a_zo=c * lda, b_zo=c * ldb, d_zo=N * Kp)
-            if rem:
-                _gemm(dy[nz * c:], x[nz * c:], slabs[nz], N, Kp, rem, prec, a_op=OP_R, b_op=OP_R, lda=lda, ldb=ldb, ldd=Kp)
-            return slabs.sum(0)
-    dW = torch.empty(N, Kp, dtype=torch.float32, device=dy.device)
-    return _gemm(dy, x, dW, N, Kp, rows, prec, a_op=OP_R, b_op=OP_R, lda=lda, ldb=ldb, ldd=Kp)
+    cut = _tn_cut(tiles, rows) if tiles < 192 and rows >= 4096 else None
+    return _slab_gemm(dy, x, N, Kp, rows, cut, prec, dy.stride(0), x.stride(0))
 
 
 def _enc_wgrad(dy, x, N, Kp, prec, bias=True):
@@ -246,6 +253,28 @@ def _dgrad(dy, wpack2d, M, N_in, K_out, prec, out_dtype, **epi):
     dx = torch.empty(M, N_in, dtype=out_dtype, device=dy.device)
     return _gemm(dy, wpack2d, dx, M, N_in, K_out, prec, b_op=OP_R, lda=dy.stride(0), ldb=wpack2d.stride(0), ldd=N_in,
                  n_store=N_in, **epi)
+
+
+def _stack_dgrad(dy, w, M, red, prec, out_dtype, lda, inner=1):
+    """dx[z] [M, Kp] = dy[z] @ W[z] over a task stack: w [Z, R, Kp] the forward's pack; dy[z] = M rows of pitch lda whose `red` >= R
+    columns (the real ones, then zeros) start (z // inner) * M * lda + (z % inner) * red elements into dy.  Under a bf16 backward, from
+    FAST_MIN_ROWS rows on: the LDS-DMA kernels on a reduction-contiguous bf16 copy W^T [Z, Kp, red] (a few MB, once per backward of the
+    node; x3f: the forward's pack is fp32), else the transposing stager on the pack itself.  The fast form reduces over all `red`
+    columns: the padding columns meet zero rows of W^T, but 0 * NaN is NaN, so they must hold FINITE values.  Invariant of this file:
+    every producer of a task-stack gradient writes its padding channels as zeros (conv / linear dgrads through n_store = pitch,
+    bn_bwd_apply, ctr_mix, upconv4_gather, cast2d with zero_pad) — never torch.empty garbage."""
+    Z, R, Kp = w.shape
+    dx = torch.empty(Z, M, Kp, dtype=out_dtype, device=dy.device)
+
+    if prec.name == "bf16" and FAST_BWD and M >= FAST_MIN_ROWS and Kp >= 128:
+        wT = w.transpose(1, 2)
+        B = (_pad_last(wT, red) if red != R else wT.contiguous()).to(torch.bfloat16)
+        K, b_op = red, OP_K
+    else:
+        B, K, b_op = w, R, OP_R
+    zi = dict(a_zi=red, b_zi=B.stride(0), d_zi=M * Kp) if inner > 1 else {}
+    return _gemm(dy, B, dx, M, Kp, K, prec, b_op=b_op, lda=lda, ldb=B.stride(1), ldd=Kp, n_store=Kp, batch=Z, batch_inner=inner,
+                 a_zo=M * lda, b_zo=B.stride(0) * inner, d_zo=M * Kp * inner, **zi)
 
 
 # =================================================================================================
@@ -637,8 +666,7 @@ class BLinearFn(Function):
                 and kmap is None and out_dtype != "split" and x.shape[-2] >= AUTO_SPLIT_MIN_ROWS
                 and ops.split_gemm_ok(ops._w2d(ws[0])[1]) and x.shape[-1] == ops._w2d(ws[0])[1])
         if auto:
-            sp = ops.split_cast(x.view(-1, x.shape[-1]))
-            xin = ops.Split(sp.hi.view(x.shape), sp.lo.view(x.shape))
+            xin = ops.split_cast(x)
         split = xlo is not None or auto
         wpack = ops.pack_linear(list(ws), prec, tag, split=split) if kmap is None else ops.pack_kmap(list(ws), N, kmap[0], kmap[1], prec, tag, split=split)
         bias = ops.stack_vec(list(bs), (tag, 'b'))
@@ -664,28 +692,10 @@ class BLinearFn(Function):
         prec = prec.bwd
         x, dy = _to_bwd(x, prec), _to_bwd(dy.contiguous(), prec)
         M, Np, Kp = x.shape[-2], pitch(N), wpack.shape[-1]
-        if layout == 'catpair':
-            az = dict(batch=Z, batch_inner=2, a_zo=M * 2 * Np, a_zi=Np)
-            lda = 2 * Np
-        else:
-            az = dict(batch=Z, batch_inner=1, a_zo=M * Np)
-            lda = Np
+        inner = 2 if layout == 'catpair' else 1
+        lda = inner * Np
         xz = x.stride(0) if (x.dim() == 3 and x.shape[0] > 1) else 0
-        bi = az['batch_inner']
-        dx = torch.empty(Z, M, Kp, dtype=getattr(ctx, "grad_dtype", None) or xdt, device=x.device)       # (a stage of FuseTailFn: the backward's dtype)
-        if prec.name == "bf16" and FAST_BWD and dy.dtype == torch.bfloat16 and M >= FAST_MIN_ROWS and Kp >= 128:
-            # dgrad on the LDS-DMA kernels: reduction-contiguous transposed pack W^T.  The reduction runs over pitch(N) columns of dy:
-            # the padding columns [N, pitch(N)) meet zero rows of W^T, but 0 * NaN is NaN, so they must hold FINITE values.  Invariant of
-            # this file: every producer of a task-stack gradient writes its padding channels as zeros (conv / linear dgrads through
-            # n_store = pitch, bn_bwd_apply, ctr_mix, upconv4_gather, cast2d with zero_pad) — never torch.empty garbage.
-            wT = _pad_last(wpack.transpose(1, 2), Np)                  # [Z, Kp, pitch(N)]: a few MB, once per backward of this node
-            if wT.dtype != torch.bfloat16:                             # x3f: the forward's pack is fp32
-                wT = wT.to(torch.bfloat16)
-            _gemm(dy, wT, dx, M, Kp, Np, prec, lda=lda, ldb=Np, ldd=Kp, b_zo=wT.stride(0) * bi, b_zi=wT.stride(0) if bi > 1 else 0,
-                  d_zo=M * Kp * bi, d_zi=M * Kp if bi > 1 else 0, n_store=Kp, **az)
-        else:
-            _gemm(dy, wpack, dx, M, Kp, N, prec, b_op=OP_R, lda=lda, ldb=Kp, ldd=Kp, b_zo=wpack.stride(0) * bi,
-                  b_zi=wpack.stride(0) if bi > 1 else 0, d_zo=M * Kp * bi, d_zi=M * Kp if bi > 1 else 0, n_store=Kp, **az)
+        dx = _stack_dgrad(dy, wpack, M, Np, prec, getattr(ctx, "grad_dtype", None) or xdt, lda, inner)      # (a stage of FuseTailFn: the backward's dtype)
         if Z == 1 and layout == 'plain':
             dW = _wgrad(dy.view(M, lda), x.reshape(M, x.shape[-1]), N, Kp, prec)[None]
         elif layout == 'catpair':
@@ -738,9 +748,7 @@ class Conv3x3Fn(Function):
         elif prec.split and x.dtype == torch.float32 and ops.split_conv_ok(Ci, Co):
             # x3f on an fp32 input (head convs, Swin, InvPT): split it HERE, so that the hi plane — the bf16 operand the backward needs
             # anyway — is what gets saved instead of the fp32 activation plus a second cast pass in the backward
-            Zx, rows, Cp = x.shape
-            sp = ops.split_cast(x.contiguous().view(Zx * rows, Cp))
-            xs = ops.Split(sp.hi.view(Zx, rows, Cp), sp.lo.view(Zx, rows, Cp))
+            xs = ops.split_cast(x.contiguous())
             y = ops.conv3x3(xs, ops.pack_conv3(list(ws), prec, tag, split=True), Co, Ci, B, H, W, prec, dil=dil, bias=bias)
             x = xs.hi
         else:
@@ -758,34 +766,9 @@ class Conv3x3Fn(Function):
         rows, Cip, Cop = x.shape[1], x.shape[2], dy.shape[2]
         wd = ops.pack_conv3(list(ws), prec, tag, transpose=True)                     # [Z, Ci, 9*Cop]
         dx = ops.conv3x3(dy, wd, Ci, Co, B, H, W, prec, flip=1, dil=dil, out_dtype=xdt)
-        conv = dict(H=H, W=W, C=Ci, Cp=Cip, dil=dil, flip=0)
-        tiles = Z * (-(-Co // 128)) * (-(-9 * Cip // 128))
-        S = _n_splits(tiles, B)                                          # slices = whole images (the gather decomposes pixel -> (y, x))
-        p256 = Z * (-(-Co // 256)) * (-(-9 * Cip // 256))
-        if (prec.name == "bf16" and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and p256 >= 64
-                and 100 * Co * 9 * Cip >= 45 * (-(-Co // 256)) * (-(-9 * Cip // 256)) * 65536):
-            # the token-major kernel takes this launch (256 x 256 tiles, one per CU): slice the pixels so that the workgroups fill whole
-            # rounds of the 256 CUs — InvPT's 576-channel convs at 128 x 128: 378 tiles = 1.48 rounds, two slices = 2.95
-            best = None
-            for cand in range(1, min(B, 8) + 1):
-                if B % cand:
-                    continue
-                cost = -(-p256 * cand // N_CUS) / cand + 0.02 * (cand - 1)        # rounds per slice + the slab it writes and re-reads
-                if best is None or cost < best[0] - 1e-9:
-                    best = (cost, cand)
-            S = best[1]
-        while B % S:
-            S -= 1
-        if S == 1:
-            dW = torch.empty(Z, Co, 9 * Cip, dtype=torch.float32, device=x.device)
-            _gemm(dy, x, dW, Co, 9 * Cip, rows, prec, a_op=OP_R, b_op=OP_CONV_R, lda=Cop, ldb=Cip, ldd=9 * Cip, batch=Z,
-                  a_zo=rows * Cop, b_zo=rows * Cip, d_zo=Co * 9 * Cip, conv=conv)
-        else:
-            c = rows // S
-            slabs = torch.empty(Z, S, Co, 9 * Cip, dtype=torch.float32, device=x.device)
-            _gemm(dy, x, slabs, Co, 9 * Cip, c, prec, a_op=OP_R, b_op=OP_CONV_R, lda=Cop, ldb=Cip, ldd=9 * Cip, batch=Z * S, batch_inner=S,
-                  a_zo=rows * Cop, a_zi=c * Cop, b_zo=rows * Cip, b_zi=c * Cip, d_zo=S * Co * 9 * Cip, d_zi=Co * 9 * Cip, conv=conv)
-            dW = slabs.sum(1)
+        S = _image_splits(Z, Co, 9 * Cip, B, prec.name == "bf16" and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16)
+        dW = _slab_gemm(dy, x, Co, 9 * Cip, rows, (S, rows // S) if S > 1 else None, prec, Cop, Cip, Z, rows * Cop, rows * Cip,
+                        b_op=OP_CONV_R, conv=dict(H=H, W=W, C=Ci, Cp=Cip, dil=dil, flip=0))
         dws = ops.unpack_grads(dW, 'conv3', [(Co, Ci, 3, 3)] * Z,       # dW[z][co, tap*Cip + ci] -> W[co, ci, tap]
                                lambda src, flat, offs: [ops.segment(src, z * Co * 9 * Cip, flat, offs[z], (Co, 9, Ci), (9 * Cip, Cip, 1), (Ci * 9, 1, 9))
                                                         for z in range(Z)])
@@ -808,9 +791,7 @@ class UpConv3x3Fn(Function):
         if prec.split and ops.split_gemm_ok(xa.shape[-1]):
             # x3f: planes of the low-resolution task features + pre-split tap matrices -> the split-plane LDS-DMA kernel; the hi planes
             # are the bf16 operands of the backward
-            Zs, M, Kp = xa.shape
-            sp = ops.split_cast(xa.reshape(Zs * M, Kp))
-            xs = ops.Split(sp.hi.view(Zs, M, Kp), sp.lo.view(Zs, M, Kp))
+            xs = ops.split_cast(xa.contiguous())
             w9 = ops.pack_upconv9(list(ws), prec, tag, split=True)
             y = ops.upconv3x3(xs, w9, Co, B, h, w, prec, bias=ops.stack_vec(list(bs), (tag, 'b')))
             ctx.save_for_backward(xs.hi, w9.hi)
@@ -830,13 +811,7 @@ class UpConv3x3Fn(Function):
         M, Kp, N9 = xa.shape[1], xa.shape[2], w9.shape[1]
         dz = _to_bwd(ops.upconv4_gather(dy, Co, B, h, w), prec)          # [Z, M, N9]
         xa = _to_bwd(xa, prec)
-        dx = torch.empty(Z, M, Kp, dtype=xdtype, device=dy.device)
-        if prec.name == "bf16" and FAST_BWD and M >= FAST_MIN_ROWS and Kp >= 128:
-            wT = w9.transpose(1, 2).contiguous().to(torch.bfloat16)      # [Z, Kp, N9]: reduction-contiguous dgrad operand (x3f: fp32 pack)
-            _gemm(dz, wT, dx, M, Kp, N9, prec, lda=N9, ldb=N9, ldd=Kp, batch=Z, a_zo=M * N9, b_zo=Kp * N9, d_zo=M * Kp, n_store=Kp)
-        else:
-            _gemm(dz, w9, dx, M, Kp, N9, prec, b_op=OP_R, lda=N9, ldb=Kp, ldd=Kp, batch=Z, a_zo=M * N9, b_zo=N9 * Kp, d_zo=M * Kp,
-                  n_store=Kp)
+        dx = _stack_dgrad(dz, w9, M, N9, prec, xdtype, N9)
         dW9 = _wgrad_batched(dz, xa, N9, Kp, M, prec, Z, N9, Kp, M * N9, M * Kp)              # [Z, N9, Kp] fp32
         Cop = N9 // 9
         dws = ops.unpack_grads(dW9, 'upconv9', [(Co, Ci, 3, 3)] * Z,    # dW9[z][tap*Cop + co, ci] -> W[co, ci, tap]
@@ -966,6 +941,27 @@ class _SubCtx:
         pass
 
 
+def _save_stages(ctx, prec, fns, subs):
+    """End of the forward of a node made of stages (Functions `fns` run on the _SubCtx `subs`): the node saves what the stages saved."""
+    ctx.save_for_backward(*[t for c in subs for t in c.saved_tensors])
+    ctx.stages = [(fn, len(c.saved_tensors), c.meta) for fn, c in zip(fns, subs)]
+    ctx.grad_dtype = prec.bwd.adt
+
+
+def _stages_backward(ctx, *grads):
+    """The stages' backwards, last stage first, each on the input gradient of the one behind it -> their gradient tuples, first stage
+    first.  The last stage is told to store its input gradient in the backward's own dtype, which the stages before it inherit."""
+    end, out = len(ctx.saved_tensors), []
+    for fn, n, meta in reversed(ctx.stages):
+        c = _SubCtx(ctx.saved_tensors[end - n:end])
+        c.meta, end = meta, end - n
+        if not out:
+            c.grad_dtype = ctx.grad_dtype
+        out.insert(0, fn.backward(c, *grads))
+        grads = out[0][:1]
+    return out
+
+
 class ConvHeadFn(Function):
     """A conv head of ALL tasks as ONE autograd node: [up4 +] Conv3x3 -> BatchNorm (batch statistics) + activation -> the per-task 1x1
     predictions — ConvHead behind the x4 resize (taskprompter.py:420, :688-698: UpConv3x3Fn -> BnActStackFn -> TaskHeadsFn) and InvPT's
@@ -1014,22 +1010,14 @@ class ConvHeadFn(Function):
         else:
             ya = BnActStackFn.forward(c2, y, C, act, training, bns, *bg, *bb)
             preds = TaskHeadsFn.forward(c3, ya, prec, ptag, *pw, *pb)
-        n1, n2 = len(c1.saved_tensors), len(c2.saved_tensors)
-        ctx.save_for_backward(*c1.saved_tensors, *c2.saved_tensors, *c3.saved_tensors)
-        ctx.sub = (n1, n2, c1.meta, c2.meta, c3.meta, Z, Stage1)
-        ctx.grad_dtype = prec.bwd.adt
+        _save_stages(ctx, prec, (Stage1, BnActStackFn, TaskHeadsFn), (c1, c2, c3))
         return preds
 
     @staticmethod
     def backward(ctx, *dps):
-        n1, n2, m1, m2, m3, Z, Stage1 = ctx.sub
-        sv = ctx.saved_tensors
-        c1, c2, c3 = _SubCtx(sv[:n1]), _SubCtx(sv[n1:n1 + n2]), _SubCtx(sv[n1 + n2:])
-        c1.meta, c2.meta, c3.meta = m1, m2, m3
-        c3.grad_dtype = ctx.grad_dtype
-        g3 = TaskHeadsFn.backward(c3, *dps)                 # (dya in grad_dtype, None, None, dW_pred x Z, db_pred x Z)
-        g2 = BnActStackFn.backward(c2, g3[0])               # (dy in grad_dtype, None x 4, dgamma x Z, dbeta x Z)
-        g1 = Stage1.backward(c1, g2[0])                     # (dfea in fea's dtype, None x 3, dW_conv x Z, db_conv x Z)
+        # g1 = (dfea in fea's dtype, None x 3, dW_conv x Z, db_conv x Z); g2 = (dy in grad_dtype, None x 4, dgamma x Z, dbeta x Z);
+        # g3 = (dya in grad_dtype, None, None, dW_pred x Z, db_pred x Z)
+        g1, g2, g3 = _stages_backward(ctx, *dps)
         return (g1[0], None, None, None, None) + tuple(g1[4:]) + tuple(g2[5:]) + tuple(g3[3:])
 
 
@@ -1050,27 +1038,18 @@ class FuseTailFn(Function):
         y1 = Conv3x3Fn.forward(c1, y0, geo, prec, tags[0], *cw, *cb)
         ya = BnActStackFn.forward(c2, y1, C, ACT_GELU, training, bns, *bg, *bb)
         if prec.split and ya.dtype == torch.float32 and ops.split_gemm_ok(ya.shape[-1]):
-            Zs, M, Kp = ya.shape
-            sp = ops.split_cast(ya.view(Zs * M, Kp))
-            fea = BLinearFn.forward(c3, sp.hi.view(Zs, M, Kp), C, 'plain', None, None, prec, tags[1], sp.lo.view(Zs, M, Kp), *w4, *b4)
+            sp = ops.split_cast(ya)
+            fea = BLinearFn.forward(c3, sp.hi, C, 'plain', None, None, prec, tags[1], sp.lo, *w4, *b4)
         else:
             fea = BLinearFn.forward(c3, ya, C, 'plain', None, None, prec, tags[1], None, *w4, *b4)
-        n1, n2 = len(c1.saved_tensors), len(c2.saved_tensors)
-        ctx.save_for_backward(*c1.saved_tensors, *c2.saved_tensors, *c3.saved_tensors)
-        ctx.sub = (n1, n2, c1.meta, c2.meta, c3.meta, Z)
-        ctx.grad_dtype = prec.bwd.adt
+        _save_stages(ctx, prec, (Conv3x3Fn, BnActStackFn, BLinearFn), (c1, c2, c3))
         return fea
 
     @staticmethod
     def backward(ctx, dfea):
-        n1, n2, m1, m2, m3, Z = ctx.sub
-        sv = ctx.saved_tensors
-        c1, c2, c3 = _SubCtx(sv[:n1]), _SubCtx(sv[n1:n1 + n2]), _SubCtx(sv[n1 + n2:])
-        c1.meta, c2.meta, c3.meta = m1, m2, m3
-        c3.grad_dtype = ctx.grad_dtype
-        g3 = BLinearFn.backward(c3, dfea)                   # (dya in grad_dtype, None x 7, dW4 x Z, db4 x Z)
-        g2 = BnActStackFn.backward(c2, g3[0])               # (dy1 in grad_dtype, None x 4, dgamma x Z, dbeta x Z)
-        g1 = Conv3x3Fn.backward(c1, g2[0])                  # (dy0 in y0's dtype, None x 3, dW_conv x Z, db_conv x Z)
+        # g1 = (dy0 in y0's dtype, None x 3, dW_conv x Z, db_conv x Z); g2 = (dy1 in grad_dtype, None x 4, dgamma x Z, dbeta x Z);
+        # g3 = (dya in grad_dtype, None x 7, dW4 x Z, db4 x Z)
+        g1, g2, g3 = _stages_backward(ctx, dfea)
         return (g1[0], None, None, None, None, None, None) + tuple(g1[4:]) + tuple(g2[5:]) + tuple(g3[8:])
 
 

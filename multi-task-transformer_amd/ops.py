@@ -89,12 +89,13 @@ def _hi(t):
     return t.hi if isinstance(t, Split) else t
 
 
-def split_cast(x2d, cols=None):
-    """fp32 [rows, ld] -> Split [rows, pitch(cols)] (mtt_split_cast)."""
-    rows = x2d.shape[0]
-    cols = cols or x2d.shape[1]
-    out = Split.empty((rows, pitch(cols)), x2d.device)
-    call("split_cast", args=[x2d, out.hi, out.lo, rows, cols, x2d.stride(0), pitch(cols)])
+def split_cast(x, cols=None):
+    """fp32 [..., rows, ld] (a matrix, or a contiguous stack of them: a task stack splits in one launch) -> Split [..., rows, pitch(cols)]
+    (mtt_split_cast)."""
+    assert x.dim() == 2 or x.is_contiguous()
+    rows, cols = x.numel() // x.shape[-1], cols or x.shape[-1]
+    out = Split.empty(x.shape[:-1] + (pitch(cols),), x.device)
+    call("split_cast", args=[x, out.hi, out.lo, rows, cols, x.stride(-2), pitch(cols)])
     return out
 
 
@@ -606,9 +607,7 @@ def conv3x3(x, wpack, Co, Ci, B, H, W, prec, *, bias=None, colscale=None, act=AC
     if isinstance(wpack, Split) and not isinstance(x, Split):
         # x3f: the weights are pre-split planes (pack_conv3 under a split Prec); an fp32 input is split by one pass (8 bytes per element,
         # against a kernel that runs 2-3x the register-staged x3 conv's rate)
-        x = x.float().contiguous()
-        sp = split_cast(x.view(Z * rows, Cp))
-        x = Split(sp.hi.view(Z, rows, Cp), sp.lo.view(Z, rows, Cp))
+        x = split_cast(x.float().contiguous())
     assert isinstance(x, Split) == isinstance(wpack, Split), "split planes: both operands or neither"
     Cop = pitch(Co)
     if out_dtype == "split":                     # the output as hi / lo planes (the split-plane kernel's epilogue kinds 5 / 6): feeds a split-plane GEMM
@@ -667,9 +666,7 @@ def upconv3x3(x, w9, Co, B, h, w, prec, *, bias=None, colscale=None, act=ACT_NON
     if isinstance(w9, Split) and not isinstance(x, Split):
         # x3f: the nine-tap GEMM (N = 9 * pitch(Co): whole 256-wide tiles) on the split-plane LDS-DMA kernel; the fp32 task features are
         # split by one pass over the LOW-resolution stack (1 / 16 of the head maps)
-        Z, M, Kp = x.shape
-        x = split_cast(x.reshape(Z * M, Kp))
-        x = Split(x.hi.view(Z, M, Kp), x.lo.view(Z, M, Kp))
+        x = split_cast(x.contiguous())
     z = linear(x, w9, w9.shape[1], prec, out_dtype=torch.float32 if isinstance(w9, Split) else None, ldd=w9.shape[1])   # nine planes of pitch Cop each
     return upconv4_expand(z, Co, B, h, w, bias=bias, colscale=colscale, act=act)
 
